@@ -20,7 +20,12 @@ overlapped with the next job, joined before the clock stops).  Data-parallel ove
 job is an independent request, exactly the reference's one-job-per-GPU node
 model, so no collective runs inside the timed region).
 
-Model load (outside the timed region, reported as ``model_load_s``): the
+A plain run sets up the random-init pipeline, warms up, times the K jobs and
+prints the result line.  ``--dump-outputs DIR`` also writes what the last timed
+job returned (``images.npy``, ``latents.npy``; see ``dump_outputs``).
+
+``--full`` adds the model-load measurement (before the warm-up, outside the
+timed region, reported as ``model_load_s``): the
 random-init weights are written ONCE as a diffusers-layout safetensors
 directory (rank 0, /dev/shm), then every rank loads them through the
 production loader: with N > 1 ranks each reads only 1/N of the checkpoint
@@ -78,10 +83,18 @@ def parse():
     ap.add_argument("--guidance", type=float, default=7.5)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the model load: write the weights once as a safetensors directory and "
+                         "reload them through the production loader (model_load_* / load_* keys of the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed job returned (rank 0) as "
+                         "DIR/images.npy and DIR/latents.npy (float32)")
     ap.add_argument("--through-supervisor", action="store_true",
                     help="drive the real serving path: a fake hive -> Supervisor -> per-GPU ProcessExecutor "
                          "children -> router -> pipeline -> encoder -> result POST")
     a = ap.parse_args()
+    if a.dump_outputs and a.through_supervisor:
+        ap.error("--dump-outputs needs the direct path (the supervisor path returns JPEG envelopes, not arrays)")
     fam, res, steps, batch, _, _ = CONFIGS[a.config]
     a.family = a.family or fam
     a.res = a.res or res
@@ -257,7 +270,8 @@ def main():
     pipe = StableDiffusion(args.family, device=device, seed=1234)
     if args.no_graphs:
         pipe.use_graphs = False
-    load_s, load_bytes, load_read_s, load_gather_s = load_through_checkpoint(pipe, rank, world)
+    # --full: the same weights once more through a checkpoint on disk and the production loader
+    load = load_through_checkpoint(pipe, rank, world) if args.full else None
 
     prompts = ["a photograph of an astronaut riding a horse", "a watercolor fox in a snowy forest",
                "a cyberpunk city street at night, neon", "a bowl of ramen, studio lighting"]
@@ -271,7 +285,7 @@ def main():
                    generator=g, scheduler=sched, output_type="uint8")
         # JPEG/base64/sha256 envelope encoding in the encoder processes, overlapped
         # with the next job (joined before the clock stops)
-        return pool.submit(list(out.images.numpy()), "image/jpeg"), out.timings, out.latents.shape
+        return pool.submit(list(out.images.numpy()), "image/jpeg"), out.timings, out
 
     futs = []
     for i in range(args.warmup):
@@ -288,7 +302,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        f, tm, _ = job(args.warmup + i)
+        f, tm, last = job(args.warmup + i)
         f.add_done_callback(lambda _f, i=i, ts=ts: done.__setitem__(i, time.perf_counter() - ts))
         futs.append(f)
         if on_gpu:
@@ -351,19 +365,46 @@ def main():
             "ms_per_step_per_rank": [round(1000 * t / args.steps, 2) for t in per_rank],
             "dist_backend": torch.distributed.get_backend() if comm.is_dist() else None,
             "phase_ms_median": phase,
-            "model_load_s": round(load_s, 2),
-            "model_load_read_s": round(load_read_s, 3),
-            "model_load_all_gather_s": round(load_gather_s, 3),
-            "load_bytes_read_per_rank": load_bytes,
-            "model_load_read_GBps": round(load_bytes / max(load_read_s, 1e-9) / 1e9, 2),
-            "load_path": (f"safetensors dir -> native sharded byte-range reads (csrc/host/csk_io.cpp) + "
-                          f"{'RCCL' if on_gpu else 'gloo'} all_gather of the raw bytes" if world > 1 else
-                          "safetensors dir -> native threaded pread + pinned-ring H2D (csrc/host/csk_io.cpp)"),
         }
+        if load is not None:
+            load_s, load_bytes, load_read_s, load_gather_s = load
+            rec.update({
+                "model_load_s": round(load_s, 2),
+                "model_load_read_s": round(load_read_s, 3),
+                "model_load_all_gather_s": round(load_gather_s, 3),
+                "load_bytes_read_per_rank": load_bytes,
+                "model_load_read_GBps": round(load_bytes / max(load_read_s, 1e-9) / 1e9, 2),
+                "load_path": (f"safetensors dir -> native sharded byte-range reads (csrc/host/csk_io.cpp) + "
+                              f"{'RCCL' if on_gpu else 'gloo'} all_gather of the raw bytes" if world > 1 else
+                              "safetensors dir -> native threaded pread + pinned-ring H2D (csrc/host/csk_io.cpp)"),
+            })
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         print(json.dumps(rec), flush=True)
     pool.shutdown()
     if comm.is_dist():
         torch.distributed.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 7_000_000  # float32 elements per dumped array: the two arrays stay under 64 MB
+
+
+def dump_outputs(path, out):
+    """``--dump-outputs DIR``: what the last timed job returned to its caller
+    (rank 0's), as float32 ``.npy``: ``images`` (B, H, W, 3; the uint8 pixels,
+    0..255) and ``latents`` (B, H/8, W/8, C; the final denoised latents).  The
+    seeds, prompts and weights are functions of the arguments alone, so two
+    builds run with the same arguments can be compared array for array.  An
+    array over 28 MB (none at the BASELINE configs) is written as a fixed,
+    seeded sample of 7M of its elements (flat, in index order)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("images", out.images), ("latents", out.latents)):
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def load_through_checkpoint(pipe, rank, world):

@@ -35,15 +35,15 @@ def test_bench_rejects_world_mismatch():
 
 
 def test_failing_rank_ends_the_run_fast():
-    """A rank that dies during the model load (the others block in its
-    collective) ends the whole run within seconds, non-zero, naming the rank —
+    """A rank that dies during the model load of ``--full`` (the others block in
+    its collective) ends the whole run within seconds, non-zero, naming the rank —
     not after the 600 s process-group timeout."""
     import time
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["SDAAS_BENCH_FAIL_RANK"] = "1"
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu", "--full",
                         "--family", "tiny", "--steps", "1", "--warmup", "0", "--denoise-steps", "1", "--res", "64",
                         "--batch", "1"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     took = time.monotonic() - t0
@@ -61,13 +61,49 @@ def test_sdxl_config_two_ranks_cpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "sdxl", "--family", "tiny-xl",
                         "--gpus", "2", "--device", "cpu", "--steps", "2", "--warmup", "1", "--denoise-steps", "2",
-                        "--res", "64"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--res", "64", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert "SDXL-base 1024×1024 30-step" in rec["metric"] and rec["config"]["bench_config"] == "sdxl"
     assert rec["config"]["global_batch"] == 2 and rec["config"]["parallelism"] == "dp2"
     assert len(rec["ms_per_step_per_rank"]) == 2 and max(rec["ms_per_step_per_rank"]) <= rec["ms_per_step"] + 1e-6
     assert rec["model_load_read_s"] >= 0 and rec["model_load_all_gather_s"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_outputs_cpu(tmp_path):
+    """A plain run times its steps only (no model-load keys; those come with
+    ``--full``), ``--steps`` sets the number of timed jobs, and ``--dump-outputs``
+    writes the last timed job's images and latents as float32 ``.npy`` — the same
+    arrays from run to run, with or without ``--full``."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    recs, dumps = [], []
+    for tag, extra in (("a", []), ("b", []), ("full", ["--full"])):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu",
+                            "--family", "tiny", "--steps", "2", "--warmup", "1", "--denoise-steps", "2", "--res", "64",
+                            "--batch", "2", "--dump-outputs", str(d), *extra],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        recs.append(json.loads(lines[0]))
+        assert sorted(os.listdir(d)) == ["images.npy", "latents.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("images", "latents")})
+    for rec in recs:
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["unit"] == "images/s"
+        assert rec["higher_is_better"] is True and rec["dtype"] == "fp32"
+        assert abs(rec["value"] - 2 * 1000 / rec["ms_per_step"]) < 0.02 * rec["value"]  # batch 2 per step
+        assert len(rec["phase_ms_median"]) > 0
+    assert not [k for k in recs[0] if "load" in k] and recs[2]["model_load_s"] >= 0
+    a = dumps[0]
+    assert a["images"].shape == (2, 64, 64, 3) and a["latents"].shape == (2, 8, 8, 4)
+    assert a["images"].dtype == np.float32 and a["latents"].dtype == np.float32
+    assert np.isfinite(a["latents"]).all() and a["images"].min() >= 0 and a["images"].max() <= 255
+    assert a["images"].std() > 0
+    for other in dumps[1:]:
+        assert np.array_equal(a["images"], other["images"]) and np.array_equal(a["latents"], other["latents"])
 
 
 def test_bench_through_supervisor_cpu(tmp_path):
