@@ -6,9 +6,12 @@ reference via ``stage_1.encode_prompt`` (swarm/diffusion/diffusion_func_if.py:43
 
 MI355X path: Q/K/V/O and the gated FFN are MFMA GEMMs (tanh-GELU of wi_0
 fused into its epilogue, the residual adds fused into wo / o).  The attention
-core (77 tokens, per-head relative-position bias, key-padding mask) is a few
-batched torch matmuls: at 77 tokens it is launch-bound either way, and it runs
-once per request.
+core (77 tokens, per-head relative-position bias, key-padding mask) is one
+launch of the bias / key-length attention kernel (``ops.attention(..., bias=,
+kv_lens=)``, csrc/kernels/attn_bias.hip) on [B, S, H, D] views of the
+projections: the fp32 bias is added to the unscaled scores in the kernel and
+the padding mask travels as per-sample key counts.  CPU tensors keep the plain
+fp32 torch formula (the transformers-parity tests run there).
 """
 from __future__ import annotations
 
@@ -20,7 +23,28 @@ import os
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .layers import Linear
+
+# None: the fused attention op for bf16 tensors on the HIP path, the torch
+# formula elsewhere.  True / False force one of them (tests: the op's fp32
+# reference definition against the formula on the CPU).
+FUSED_ATTENTION: bool | None = None
+
+
+def _fused(x: torch.Tensor) -> bool:
+    if FUSED_ATTENTION is not None:
+        return FUSED_ATTENTION
+    return ops.use_hip(x) and x.dtype == torch.bfloat16
+
+
+def key_lens(mask: torch.Tensor | None):
+    """Key-padding mask [B, S] (bool) -> per-sample key counts (int32 [B]) for
+    the attention op, computed on the mask's device with no host read.
+    ``T5Tokenizer`` (and BLIP-2's query-prefix + prompt layout) only produce
+    PREFIX masks (ones, then zeros), for which "the first n keys" is the mask
+    exactly; a mask with holes is not representable this way."""
+    return None if mask is None else mask.sum(1).to(torch.int32)
 
 
 @dataclasses.dataclass
@@ -94,10 +118,14 @@ class _AttnLayer(nn.Module):
         self.SelfAttention = _SelfAttention(c, has_bias)
         self.layer_norm = T5RMSNorm(c.d_model, c.eps)
 
-    def forward(self, x, bias, mask):
+    def forward(self, x, bias, mask, lens=None):
         a = self.SelfAttention
         b, s, _ = x.shape
         h = self.layer_norm(x)
+        if _fused(x):  # lens = key_lens(mask), computed once per forward by the caller
+            q, k, v = (m(h).view(b, s, a.c.heads, a.c.d_kv) for m in (a.q, a.k, a.v))
+            o = ops.attention(q, k, v, 1.0, bias=bias, kv_lens=lens)  # T5: no 1/sqrt(d) scaling
+            return a.o(o.reshape(b, s, -1), residual=x)
         q, k, v = (m(h).view(b, s, a.c.heads, a.c.d_kv).transpose(1, 2).float() for m in (a.q, a.k, a.v))
         scores = q @ k.transpose(-1, -2) + bias[None]  # T5: no 1/sqrt(d) scaling
         if mask is not None:
@@ -143,16 +171,25 @@ class T5Encoder(nn.Module):
         dt = self.shared.weight.dtype
         x = self.shared(ids).to(dt)
         bias = self.encoder.block[0].layer[0].SelfAttention.position_bias(ids.shape[1], ids.device)
+        lens = None
+        if _fused(x):
+            bias, lens = bias.contiguous(), key_lens(mask)
         for blk in self.encoder.block:
-            x = blk.layer[0](x, bias, mask)
+            x = blk.layer[0](x, bias, mask, lens)
             x = blk.layer[1](x)
         return self.encoder.final_layer_norm(x)
 
 
-def _attend(a: "_SelfAttention", h, kv_src, bias, mask):
-    """softmax(q k^T + bias [+ key mask]) v for one T5 attention (no 1/sqrt(d))."""
+def _attend(a: "_SelfAttention", h, kv_src, bias, mask, lens=None):
+    """softmax(q k^T + bias [+ key mask]) v for one T5 attention (no 1/sqrt(d)).
+    ``lens`` = key_lens(mask), used by the fused op in place of the mask."""
     b, s, _ = h.shape
     t = kv_src.shape[1]
+    if _fused(h):
+        q = a.q(h).view(b, s, a.c.heads, a.c.d_kv)
+        k = a.k(kv_src).view(b, t, a.c.heads, a.c.d_kv)
+        v = a.v(kv_src).view(b, t, a.c.heads, a.c.d_kv)
+        return ops.attention(q, k, v, 1.0, bias=bias, kv_lens=lens).reshape(b, s, -1)
     q = a.q(h).view(b, s, a.c.heads, a.c.d_kv).transpose(1, 2).float()
     k = a.k(kv_src).view(b, t, a.c.heads, a.c.d_kv).transpose(1, 2).float()
     v = a.v(kv_src).view(b, t, a.c.heads, a.c.d_kv).transpose(1, 2).float()
@@ -181,9 +218,10 @@ class _CrossLayer(nn.Module):
         self.EncDecAttention = _SelfAttention(c, False)
         self.layer_norm = T5RMSNorm(c.d_model, c.eps)
 
-    def forward(self, x, enc, enc_mask):
+    def forward(self, x, enc, enc_mask, enc_lens=None):
         h = self.layer_norm(x)
-        return self.EncDecAttention.o(_attend(self.EncDecAttention, h, enc, None, enc_mask).to(x.dtype), residual=x)
+        return self.EncDecAttention.o(_attend(self.EncDecAttention, h, enc, None, enc_mask, enc_lens).to(x.dtype),
+                                      residual=x)
 
 
 class _DecBlock(nn.Module):
@@ -217,8 +255,11 @@ class T5Seq2Seq(nn.Module):
     @torch.no_grad()
     def encode(self, x: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:
         bias = self.encoder.block[0].layer[0].SelfAttention.position_bias(x.shape[1], x.device)
+        lens = None
+        if _fused(x):
+            bias, lens = bias.contiguous(), key_lens(mask)
         for blk in self.encoder.block:
-            x = blk.layer[0](x, bias, mask)
+            x = blk.layer[0](x, bias, mask, lens)
             x = blk.layer[1](x)
         return self.encoder.final_layer_norm(x)
 
@@ -231,9 +272,12 @@ class T5Seq2Seq(nn.Module):
         s = x.shape[1]
         bias = self.decoder.block[0].layer[0].SelfAttention.position_bias(s, x.device, bidirectional=False)
         bias = bias.masked_fill(torch.ones(s, s, dtype=torch.bool, device=x.device).triu(1)[None], float("-inf"))
+        enc_lens = None
+        if _fused(x):  # the causal mask stays as -inf entries of the bias
+            bias, enc_lens = bias.contiguous(), key_lens(enc_mask)
         for blk in self.decoder.block:
             x = blk.layer[0](x, bias)
-            x = blk.layer[1](x, enc, enc_mask)
+            x = blk.layer[1](x, enc, enc_mask, enc_lens)
             x = blk.layer[2](x)
         h = self.decoder.final_layer_norm(x[:, -1:])
         if self.tie:  # tied head (original T5): transformers rescales by d_model^-0.5

@@ -7,9 +7,12 @@ sentencepiece tokenizer (transformers ``XLMRobertaTokenizer``).
 
 MI355X path: the post-LN RoBERTa blocks run on the MFMA GEMM (packed QKV,
 fused bias / GELU / residual epilogues) and the flash attention kernel.  The
-tokenizer pads to 77 and the encoder masks the padding keys; here every prompt
-runs as its 77 queries against only its real (non-pad) keys — the masked
-computation exactly, with no key-padding mask in the attention kernel.
+tokenizer pads to 77 and the encoder masks the padding keys.  On the HIP path
+the whole (CFG) batch runs in one pass and every row's real (non-pad) key count
+goes to the attention kernel as a device tensor (``ops.attention(...,
+kv_lens=)``): no host read, so the encoder is captured in the text hipGraph
+like every other family's.  CPU tensors run prompt by prompt, each as its 77
+queries against only its real keys — the same masked computation.
 
 ``projection_state`` = transformation(last hidden state), or with
 ``has_pre_transformation`` (AltDiffusion-m9) transformation_pre(pre_LN(hidden
@@ -110,11 +113,47 @@ class XLMRobertaSeries(nn.Module):
         x = blk.ln1(a.o(o.reshape(b, s, a.heads * a.dh), residual=x))
         return blk.ln2(blk.fc2(blk.fc1(x, act="gelu"), residual=x))
 
+    def _layer_lens(self, blk: PostLNBlock, x, lens):
+        """Post-LN block, whole batch: sample b attends to its first ``lens[b]`` keys."""
+        a = blk.attn
+        a._ensure()
+        b, s, _ = x.shape
+        qkv = ops.gemm(x, a.w_in, a.b_in).view(b, s, 3, a.heads, a.dh)
+        o = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], a.scale, kv_lens=lens)
+        x = blk.ln1(a.o(o.reshape(b, s, a.heads * a.dh), residual=x))
+        return blk.ln2(blk.fc2(blk.fc1(x, act="gelu"), residual=x))
+
+    def forward_batched(self, ids: torch.Tensor):
+        """``forward`` with all rows in one pass: the per-row key count goes to
+        the attention op as a device tensor (``kv_lens``), so nothing is read
+        back to the host and the encoder can be captured in a hipGraph.  Like
+        the per-row path this takes the real tokens to be a prefix of the row
+        (``XLMRTokenizer`` pads at the end)."""
+        cfg = self.cfg
+        dt = self.word_embeddings.weight.dtype
+        real = ids != cfg.pad_token_id
+        if cfg.use_attention_mask:
+            lens = real.sum(1).clamp_min(1).to(torch.int32)
+        else:
+            lens = torch.full((ids.shape[0],), ids.shape[1], dtype=torch.int32, device=ids.device)
+        # RoBERTa create_position_ids_from_input_ids: real tokens count from pad + 1, pads sit at pad
+        pos = (torch.cumsum(real.int(), 1) * real.int() + cfg.pad_token_id).long()
+        x = self.word_embeddings(ids) + self.position_embeddings(pos) + self.token_type_embeddings.weight[0]
+        x = self.emb_ln(x.to(dt))
+        prev = x
+        for blk in self.layers:
+            prev, x = x, self._layer_lens(blk, x, lens)
+        if cfg.pre_transformation:
+            return self.transformation_pre(self.pre_ln(prev)), None, None, None
+        return self.transformation(x), None, None, None
+
     def forward(self, ids: torch.Tensor):
         """ids [B, S] (padded with pad_token_id) -> (projection_state [B, S, project_dim],
         None, None, None): the CLIPTextModel tuple layout the SD pipeline reads."""
         cfg = self.cfg
         dt = self.word_embeddings.weight.dtype
+        if ids.is_cuda:  # (reference mode included: its kv_lens definition reads nothing back either)
+            return self.forward_batched(ids)
         outs = []
         for r in range(ids.shape[0]):
             t = ids[r:r + 1]

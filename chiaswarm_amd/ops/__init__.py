@@ -750,12 +750,52 @@ def _ref_attention(q, k, v, scale, causal):
     return o.permute(0, 2, 1, 3).to(q.dtype).contiguous()
 
 
-def attention(q, k, v, scale=None, causal=False, kv_len=None):
+def _ref_attention_bias(q, k, v, scale, causal=False, bias=None, kv_lens=None):
+    """softmax(q k^T * scale + bias) v over each sample's first ``kv_lens[b]``
+    keys, in fp32.  Key j of query i is visible iff j < min(kv_lens[b], Skv) and,
+    if ``causal``, j <= i + (Skv - Sq) (aligned against the tensor's Skv:
+    padding-mask semantics).  A query row with no visible key (or whose visible
+    bias entries are all -inf) gives zeros."""
+    B, Sq, H, _ = q.shape
+    Skv = k.shape[1]
+    qt, kt, vt = (t.permute(0, 2, 1, 3).float() for t in (q, k, v))
+    s = (qt @ kt.transpose(-1, -2)) * scale
+    if bias is not None:
+        s = s + bias.float().expand(B, H, Sq, Skv)
+    if kv_lens is not None:
+        hidden = torch.arange(Skv, device=s.device)[None, :] >= kv_lens.reshape(B, 1).to(torch.long)
+        s = s.masked_fill(hidden[:, None, None, :], float("-inf"))
+    if causal:
+        mask = torch.ones(Sq, Skv, dtype=torch.bool, device=s.device).triu(1 + Skv - Sq)
+        s = s.masked_fill(mask, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - torch.where(torch.isinf(m), torch.zeros_like(m), m))  # all -inf row: exp(-inf) = 0
+    l = p.sum(-1, keepdim=True)
+    o = (p @ vt) / torch.where(l > 0, l, torch.ones_like(l))
+    return o.permute(0, 2, 1, 3).to(q.dtype).contiguous()
+
+
+def attention(q, k, v, scale=None, causal=False, kv_len=None, *, bias=None, kv_lens=None):
     """softmax(q k^T * scale) v for [B, S, H, D] views; returns [B, Sq, H, D].
     ``kv_len`` (int32 device tensor [1]): only the first kv_len keys are used;
-    read on the device by the HIP kernel (hipGraph-capturable decode step)."""
+    read on the device by the HIP kernel (hipGraph-capturable decode step).
+
+    ``bias`` (fp32, broadcastable to [B, H, Sq, Skv]) is added to the scaled
+    scores, unscaled; entries may be -inf.  ``kv_lens`` (int32 [B]) gives every
+    sample its own key count: a key-padding mask, read on the device.  Unlike
+    ``kv_len`` it does not move the causal diagonal, and a query row left with
+    no visible key returns zeros.  ``kv_len`` and ``kv_lens`` exclude each other."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if bias is not None or kv_lens is not None:
+        if kv_len is not None:
+            raise ValueError("attention: kv_len (KV-cache fill level) and kv_lens (per-sample key padding) "
+                             "cannot be combined")
+        if use_hip(q):
+            from . import hip_ops
+
+            return hip_ops.attention_bias(q, k, v, scale, causal, bias, kv_lens)
+        return _ref_attention_bias(q, k, v, scale, causal, bias, kv_lens)
     if use_hip(q):
         from . import hip_ops
 

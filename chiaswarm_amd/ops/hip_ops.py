@@ -627,6 +627,67 @@ def attention(q, k, v, scale, causal=False, kv_len=None):
     return o
 
 
+sig("csk_attention_bias", c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int,
+    c_int, c_float, c_int, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_void_p)
+sig("csk_set_attn_bias_waves", c_int)
+
+
+def set_attn_bias_waves(n: int):
+    """Waves per workgroup of the bias / key-length attention: 0 auto, 1 / 2 / 4
+    (16 query rows per wave; A/B knob of tools/attnbiasbench.py)."""
+    _lib.call("csk_set_attn_bias_waves", int(n))
+
+
+def attention_bias(q, k, v, scale, causal=False, bias=None, kv_lens=None):
+    """softmax(q k^T * scale + bias) v over each sample's first ``kv_lens[b]``
+    keys (csrc/kernels/attn_bias.hip).  ``bias``: fp32 device tensor
+    broadcastable to [B, H, Sq, Skv] (expanded here: broadcast dims become
+    stride 0); ``kv_lens``: int32 device tensor [B], read by the kernel.  No
+    host read, no allocation but the output: graph-capturable."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _bf16(t, "attention_bias." + n)
+        if t.dim() != 4:
+            raise ValueError(f"attention_bias.{n}: expected [B, S, H, D], got {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise TypeError(f"attention_bias.{n}: must be a device tensor")
+        if t.stride(-1) != 1:
+            raise ValueError("attention_bias: last dim must be contiguous")
+    B, Sq, H, D = q.shape
+    Skv = k.shape[1]
+    if k.shape != (B, Skv, H, D) or v.shape != (B, Skv, H, D):
+        raise ValueError(f"attention_bias: k / v {tuple(k.shape)} / {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    if bias is not None:
+        if bias.dtype != torch.float32 or not bias.is_cuda:
+            raise TypeError("attention_bias: bias must be a float32 device tensor")
+        if bias.dim() == 0:
+            bias = bias.reshape(1)
+        full = (B, H, Sq, Skv)
+        if bias.dim() > 4 or any(n not in (1, m) for n, m in zip(bias.shape[::-1], full[::-1])):
+            raise ValueError(f"attention_bias: bias {tuple(bias.shape)} does not broadcast to {full}")
+        if Skv > 1 and (bias.shape[-1] != Skv or bias.stride(-1) != 1):
+            bias = bias.expand(*bias.shape[:-1], Skv).contiguous()  # the kernel reads 4 consecutive keys
+        bias = bias.expand(B, H, Sq, Skv)
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32 or not kv_lens.is_cuda:
+            raise TypeError("attention_bias: kv_lens must be an int32 device tensor")
+        if tuple(kv_lens.shape) != (B,) or kv_lens.stride(0) != 1:
+            raise ValueError(f"attention_bias: kv_lens must be a contiguous [B = {B}] tensor, got {tuple(kv_lens.shape)}")
+    if D > 128 or D % 8 or D < 8:  # shapes the kernel does not take: the reference formula on the device
+        from . import _ref_attention_bias
+
+        return _ref_attention_bias(q, k, v, scale, causal, bias, kv_lens)
+    o = torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device)
+    if o.numel() == 0:
+        return o
+    if Skv == 0:
+        return o.zero_()
+    st = (c_int64 * 12)(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o.stride()[:3])
+    bst = (c_int64 * 3)(*bias.stride()[:3]) if bias is not None else None
+    _lib.call("csk_attention_bias", _p(o), _p(q), _p(k), _p(v), st, B, H, Sq, Skv, D, float(scale),
+              int(bool(causal)), _p(bias), bst, _p(kv_lens), _s())
+    return o
+
+
 def attention_split(q, k, v, scale, split, o=None):
     """d = 64 non-causal attention with the keys split over ``split`` workgroups
     per query block (fp32 partials in a torch workspace, then a combine pass)."""

@@ -324,9 +324,7 @@ class StableDiffusion:
         """(context, added_cond or None, cross-attention K/V tuple)."""
         texts = (negatives + prompts) if cfg else prompts
         ids = tuple(tok(texts).to(self.device) for tok in self.tokenizers)
-        # (XLM-RoBERTa cuts each prompt's keys to its real tokens, a host-side
-        # length: that encoder runs eagerly, not as a captured graph)
-        if self.use_graphs and with_kv and not any(isinstance(c, XLMRConfig) for c in self.family.text):
+        if self.use_graphs and with_kv:
             if not hasattr(self, "_text_graphs"):
                 from .graphs import GraphCache
 
