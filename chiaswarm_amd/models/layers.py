@@ -58,10 +58,14 @@ class Conv2d(nn.Conv2d, Prepared):
         return self.wp
 
     def forward(self, x, residual=None, up2x=False, bias2d=None, padding=None, act=None, out_scale=1.0,
-                out=None, gn_stats=False, row_stats=False, residual2=None, res_scale=1.0):  # type: ignore[override]
+                out=None, gn_stats=False, row_stats=False, residual2=None, res_scale=1.0,
+                norm=None, norm_optional=False):  # type: ignore[override]
+        """``norm``: ``GroupNorm.after_conv(...)`` of the GroupNorm that consumes
+        the output (``ops.conv2d``): returns the normalised tensor, or
+        (normalised, raw) when the raw output is kept."""
         kh, kw = self.kernel_size
         if (kh == 1 and kw == 1 and self.stride == (1, 1) and not up2x and act is None and out_scale == 1.0
-                and out is None and x.is_contiguous() and residual2 is None and res_scale == 1.0):
+                and out is None and x.is_contiguous() and residual2 is None and res_scale == 1.0 and norm is None):
             w2 = self.weight.view(self.out_channels, self.in_channels)
             gr = x.shape[1] * x.shape[2] if (gn_stats and bias2d is None and x.dim() == 4) else 0
             y = ops.gemm(x, w2, self.bias, residual=residual, gn_rows=gr, row_stats=row_stats and bias2d is None)
@@ -75,7 +79,8 @@ class Conv2d(nn.Conv2d, Prepared):
             pad = padding
         return ops.conv2d(x, self._wp(), self.bias, self.stride[0], pad, residual=residual,
                           up2x=up2x, bias2d=bias2d, act=act, out_scale=out_scale, out=out,
-                          dilation=max(self.dilation), gn_stats=gn_stats, residual2=residual2, res_scale=res_scale)
+                          dilation=max(self.dilation), gn_stats=gn_stats, residual2=residual2, res_scale=res_scale,
+                          norm=norm, norm_optional=norm_optional)
 
 
 class Conv1d(nn.Conv1d, Prepared):
@@ -116,7 +121,27 @@ class ConvTranspose1d(nn.ConvTranspose1d, Prepared):
 
 class GroupNorm(nn.GroupNorm):
     def forward(self, x, silu=False):  # type: ignore[override]
+        pre = getattr(x, "_csk_prenorm", None)
+        if pre is not None and pre[0] == self._key(silu):
+            return pre[1]  # the producer conv already applied this norm (ResnetBlock2D next_norm)
         return ops.group_norm(x, self.weight, self.bias, self.num_groups, self.eps, silu=silu)
+
+    def _key(self, silu):
+        w, b = self.weight, self.bias
+        return (w.data_ptr(), w._version, b.data_ptr(), b._version, self.num_groups, self.eps, bool(silu))
+
+    def attach(self, raw, normed, silu=False):
+        """Carry ``normed`` = this norm of ``raw`` on ``raw`` (as ``_csk_gn`` carries
+        statistics): ``forward(raw)`` returns it; any other consumer ignores it.
+        As with ``_csk_gn``, ``raw`` must not be modified in place while it carries
+        the attribute: the key covers this norm's parameters, not ``raw``'s values."""
+        if normed is not None:
+            raw._csk_prenorm = (self._key(silu), normed)
+        return raw
+
+    def after_conv(self, silu=False, keep_raw=False):
+        """This norm as the ``norm`` argument of the conv that produces its input."""
+        return (self.weight, self.bias, self.num_groups, self.eps, silu, keep_raw)
 
 
 class LayerNorm(nn.LayerNorm):
@@ -440,7 +465,17 @@ class ResnetBlock2D(nn.Module):
         self.conv_shortcut = Conv2d(cin, cout, 1, padding=0) if cin != cout else None
         self.out_channels = cout
 
-    def forward(self, x, temb_proj=None):
+    def _conv2(self, h, sc, next_norm):
+        """conv2 + shortcut; ``next_norm``: the GroupNorm the caller knows to
+        consume the block output next (a transformer's input norm).  A split-K
+        conv2 then applies it in its reduce kernel beside the raw output and the
+        result rides on the output (``GroupNorm.attach``)."""
+        if next_norm is None or next_norm.weight.dim() != 1:
+            return self.conv2(h, residual=sc, gn_stats=True)  # block output usually feeds the next GroupNorm
+        yn, out = self.conv2(h, residual=sc, norm=next_norm.after_conv(keep_raw=True), norm_optional=True)
+        return next_norm.attach(out, yn)
+
+    def forward(self, x, temb_proj=None, next_norm=None):
         """``temb_proj``: this block's [B, Cout] time projection (already
         computed by the model's batched time-embedding GEMM).  A 1x1 shortcut
         runs on a side stream, overlapping norm1 / conv1 / norm2."""
@@ -449,12 +484,13 @@ class ResnetBlock2D(nn.Module):
             if self.conv_shortcut is not None:
                 sc = self.conv_shortcut(x)
         h = self.norm1(x, silu=True)
-        h = self.conv1(h, bias2d=temb_proj, gn_stats=True)  # norm2's statistics from conv1's epilogue
-        h = self.norm2(h, silu=True)
+        # nobody but norm2 reads conv1's output: a split-K conv1 applies norm2 in its
+        # reduce kernel, any other takes norm2's statistics from its epilogue
+        h = self.conv1(h, bias2d=temb_proj, norm=self.norm2.after_conv(silu=True))
         br.join()
-        return self.conv2(h, residual=sc, gn_stats=True)  # block output usually feeds the next GroupNorm
+        return self._conv2(h, sc, next_norm)
 
-    def forward_cat(self, a, b, temb_proj=None):
+    def forward_cat(self, a, b, temb_proj=None, next_norm=None):
         """forward() of the channel concat [a | b] (a UNet skip connection)
         without materialising the concat on the HIP path: norm1 reads both
         tensors in place and the 1x1 shortcut runs as two accumulating GEMMs
@@ -466,16 +502,15 @@ class ResnetBlock2D(nn.Module):
             hn = ops.group_norm_cat(a, b, self.norm1.weight, self.norm1.bias, self.norm1.num_groups,
                                     self.norm1.eps, silu=True)
         if hn is None:
-            return self.forward(ops.cat_channels(a, b), temb_proj)
+            return self.forward(ops.cat_channels(a, b), temb_proj, next_norm)
         w = sc_conv.weight.view(sc_conv.out_channels, sc_conv.in_channels)
         ca = a.shape[-1]
         with ops.side_branch(a) as br:  # shortcut GEMMs overlap conv1 / norm2
             sc = ops.gemm(a, w[:, :ca])
             sc = ops.gemm(b, w[:, ca:], sc_conv.bias, residual=sc)
-        h = self.conv1(hn, bias2d=temb_proj, gn_stats=True)
-        h = self.norm2(h, silu=True)
+        h = self.conv1(hn, bias2d=temb_proj, norm=self.norm2.after_conv(silu=True))
         br.join()
-        return self.conv2(h, residual=sc, gn_stats=True)
+        return self._conv2(h, sc, next_norm)
 
 
 class Downsample2D(nn.Module):

@@ -364,7 +364,12 @@ class UNet2DConditionModel(Prepared):
         for blk in self.down_blocks:
             for j, r in enumerate(blk.resnets):
                 tp = next(tprojs)
-                h = r(h, tp[:half] if half else tp)
+                # a transformer's input GroupNorm is the only reader of the normalised
+                # block output: a split-K conv2 applies it in its reduce.  (Outputs that
+                # are skip connections stay raw-only: their concat GroupNorm later reads
+                # the epilogue statistics the fused reduce does not emit.)
+                h = r(h, tp[:half] if half else tp,
+                      next_norm=blk.attentions[j].norm if blk.attentions is not None and not half else None)
                 if blk.attentions is not None:
                     h = run_attn(blk.attentions[j], h, dup=bool(half))
                     half = 0
@@ -380,7 +385,7 @@ class UNet2DConditionModel(Prepared):
         elif down_residuals is not None:
             skips = [s + r.to(s.dtype) for s, r in zip(skips, down_residuals)]
 
-        h = self.mid_block.resnets[0](h, next(tprojs))
+        h = self.mid_block.resnets[0](h, next(tprojs), next_norm=self.mid_block.attentions[0].norm)
         h = run_attn(self.mid_block.attentions[0], h)
         h = self.mid_block.resnets[1](h, next(tprojs))
         if control is not None:
@@ -391,7 +396,8 @@ class UNet2DConditionModel(Prepared):
         for blk in self.up_blocks:
             for j, r in enumerate(blk.resnets):
                 s = skips.pop()
-                h = r.forward_cat(h, s, next(tprojs))
+                h = r.forward_cat(h, s, next(tprojs),
+                                  next_norm=blk.attentions[j].norm if blk.attentions is not None else None)
                 if blk.attentions is not None:
                     h = run_attn(blk.attentions[j], h)
             if blk.upsamplers is not None:

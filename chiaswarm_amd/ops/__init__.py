@@ -532,7 +532,8 @@ def _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, 
 
 
 def conv2d(x, wp, bias=None, stride=1, padding=1, residual=None, up2x=False, bias2d=None, act=None,
-           out_scale=1.0, out=None, dilation=1, gn_stats=False, residual2=None, res_scale=1.0, out_u8=False):
+           out_scale=1.0, out=None, dilation=1, gn_stats=False, residual2=None, res_scale=1.0, out_u8=False,
+           norm=None, norm_optional=False):
     """NHWC conv.  ``wp``: packed [Cout, kh, kw, Cin].  ``up2x`` fuses a
     nearest-neighbour x2 upsample into the input addressing; ``bias2d`` [B, Cout]
     is a per-sample channel bias (ResNet time-embedding add) fused in the
@@ -543,19 +544,37 @@ def conv2d(x, wp, bias=None, stride=1, padding=1, residual=None, up2x=False, bia
     ``residual2`` / ``res_scale``: y = act(...) * out_scale + res_scale *
     residual + residual2 (Real-ESRGAN's nested "* 0.2 + x" in one epilogue;
     ``out`` may alias ``residual2``).  ``out_u8``: the output is a uint8 image,
-    round(clamp(y, 0, 1) * 255) (Real-ESRGAN's RGB conv_last)."""
+    round(clamp(y, 0, 1) * 255) (Real-ESRGAN's RGB conv_last).
+    ``norm = (gamma, beta, groups, eps, silu, keep_raw)``: the GroupNorm that
+    consumes the output, i.e. ``group_norm(conv2d(...), gamma, beta, groups, eps,
+    silu)``; the call returns the normalised tensor, or (normalised, raw) with
+    ``keep_raw`` (``out=``, the raw output's buffer, needs it).  A split-K plan on the HIP path applies it in the reduce
+    kernel, so the raw tensor is never written unless kept.  ``norm_optional``
+    (with ``keep_raw``): apply the norm only where it costs no extra kernel,
+    else return (None, raw) and leave it to the consumer of the raw tensor."""
     if use_hip(x):
         from . import hip_ops
 
         return hip_ops.conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, out, dilation,
-                              gn_stats, residual2=residual2, res_scale=res_scale, out_u8=out_u8)
+                              gn_stats, residual2=residual2, res_scale=res_scale, out_u8=out_u8, norm=norm,
+                              norm_optional=norm_optional)
+    if norm is not None and (out_u8 or residual2 is not None or res_scale != 1.0):
+        raise ValueError("conv2d: norm with out_u8 / residual2 / res_scale")
+    if norm is not None and out is not None and not norm[5]:
+        raise ValueError("conv2d: out= with norm is the raw output: it needs keep_raw")
     y = _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, dilation,
                     residual2, res_scale)
     if out_u8:
         y = (y.float().clamp(0, 1) * 255).round().to(torch.uint8)
     if out is not None:
         out.copy_(y)
-        return out
+        y = out
+    if norm is not None:
+        gamma, beta, groups, eps, silu, keep_raw = norm
+        if norm_optional and keep_raw:
+            return None, y
+        yn = _ref_group_norm(y, gamma, beta, groups, eps, silu)
+        return (yn, y) if keep_raw else yn
     return y
 
 

@@ -346,17 +346,89 @@ CONV_TILE64 = os.environ.get("CSK_CONV_TILE64", "1") == "1"  # the Cout = 64 ins
 CONV_TILE_NARROW_MIN_PX = int(os.environ.get("CSK_CONV_TILE_NARROW_MIN_PX", str(1 << 18)))
 CONV_TILE_STATS = [0]  # calls (tests assert the kernel ran)
 
+# Split-K conv whose reduce also applies the GroupNorm (+ SiLU) that follows it
+# (gemm.hip splitk_reduce_gn_apply_kernel; conv2d's ``norm`` argument).
+# CSK_SKGN_FUSED=0 / set_skgn_fused(False): the split-K reduce and the
+# GroupNorm apply stay two kernels.
+sig("csk_set_skgn_fused", c_int)
+sig("csk_set_skgn_min_wg", c_int)
+sig("csk_get_skgn_min_wg")
+sig("csk_get_skr_unroll")
+sig("csk_splitk_gn_fused_ok", c_int, c_int, c_int, c_int)
+sig("csk_conv2d_gn", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
+    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_void_p)
+SKGN_FUSED = os.environ.get("CSK_SKGN_FUSED", "1") == "1"
+# conv2d(norm=...) calls: (norm applied in the reduce, conv + GroupNorm kernels here,
+# norm_optional: raw returned and the norm left to its consumer)
+SKGN_STATS = [0, 0, 0]
+SKGN_SITES = None  # tools: a list here collects (B, Ho, Wo, Cin, Cout, split, keep_raw) of every fused call
+
+
+def set_skgn_fused(on: bool):
+    global SKGN_FUSED
+    SKGN_FUSED = bool(on)
+    _lib.call("csk_set_skgn_fused", int(SKGN_FUSED))
+
+
+def set_skgn_min_wg(n: int) -> int:
+    """Smallest grid (samples x groups) the fused kernel takes; returns the previous value."""
+    old = _lib.call_int("csk_get_skgn_min_wg")
+    _lib.call("csk_set_skgn_min_wg", int(n))
+    return old
+
+
+def _eff_split(split, K):
+    """The split count the library runs for a requested ``split`` > 1 (gemm.hip
+    dispatch: whole 64-wide K steps per split, empty splits dropped)."""
+    if split <= 1:
+        return split
+    kchunk = -(-(-(-K // 64)) // split) * 64
+    return -(-K // kchunk)
+
+
+def _skgn_ok(split, K, M, Cout, rows_per_b, ys, code, gamma, beta, groups, silu, bias, bias2d, b2s, residual, rs,
+             out, keep_raw):
+    """The fused reduce + GroupNorm apply takes this conv: a split-K plan, no
+    activation, shared [C] affine, 8-byte aligned 4-channel vectors everywhere,
+    one sample's group within the kernel's register budget."""
+    if not SKGN_FUSED or _eff_split(split, K) <= 1 or code != 0 or gamma.dim() != 1 or silu not in (True, False):
+        return False
+    if gamma.dtype != torch.bfloat16 or beta.dtype != torch.bfloat16 or gamma.numel() != Cout or beta.numel() != Cout:
+        return False
+    if not (gamma.is_contiguous() and beta.is_contiguous()):
+        return False
+    for t in (gamma, beta, bias, bias2d, residual, out if keep_raw else None):
+        if t is not None and t.data_ptr() % 8:
+            return False
+    if (keep_raw and ys % 4) or (residual is not None and rs % 4) or (bias2d is not None and b2s % 4):
+        return False
+    return _lib.call_int("csk_splitk_gn_fused_ok", M, Cout, rows_per_b, int(groups)) > 0
+
 
 def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_scale=1.0, out=None, dilation=1,
-           gn_stats=False, residual2=None, res_scale=1.0, out_u8=False):
+           gn_stats=False, residual2=None, res_scale=1.0, out_u8=False, norm=None, norm_optional=False):
     """NHWC conv.  ``x``, ``residual`` and ``out`` may be channel-slice views of
     wider NHWC buffers (last dim contiguous): the kernel takes their pixel
     strides, so dense/concat blocks need no copies.  ``residual2`` /
     ``res_scale`` (y = ... * out_scale + res_scale * residual + residual2, ``out``
     may alias ``residual2``) run in the halo-tile kernel's epilogue, elsewhere as
     one extra pass.  ``out_u8``: uint8 image output round(clamp(y, 0, 1) * 255)
-    (the halo-tile kernel stores it directly for Cout < 16)."""
+    (the halo-tile kernel stores it directly for Cout < 16).
+    ``norm = (gamma, beta, groups, eps, silu, keep_raw)``: the GroupNorm (+ SiLU)
+    that consumes the output; returns the normalised tensor, or (normalised, raw)
+    with ``keep_raw``.  A split-K plan applies it in its reduce kernel
+    (SKGN_STATS[0]); anything else is this conv followed by ``group_norm``, or,
+    with ``norm_optional`` (and ``keep_raw``), returns (None, raw) and leaves the
+    norm to the consumer of the raw tensor (its epilogue statistics attached)."""
     from . import conv_out_size, norm_padding
+
+    if norm is not None:
+        if out_u8 or residual2 is not None or res_scale != 1.0:
+            raise ValueError("conv2d: norm with out_u8 / residual2 / res_scale")
+        if out is not None and not norm[5]:
+            raise ValueError("conv2d: out= with norm is the raw output: it needs keep_raw")
+        gn_stats = True  # where the reduce does not apply the norm, its statistics come from the conv
 
     _bf16(x, "conv.x")
     _bf16(wp, "conv.w")
@@ -379,15 +451,17 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
     if out_u8:
         return _conv2d_u8(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, out, dilation,
                           residual2, res_scale, Ho, Wo)
-    if out is None:
-        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
-    ys = _pix_stride(out)
-    if out.shape != (B, Ho, Wo, Cout) or ys is None:
+    oshape = (B, Ho, Wo, Cout)
+    if out is None and (norm is None or norm[5]):
+        out = torch.empty(oshape, dtype=torch.bfloat16, device=x.device)
+    # norm without keep_raw: the raw tensor is allocated only if the reduce does not apply the norm
+    ys = Cout if out is None else _pix_stride(out)
+    if out is not None and (out.shape != oshape or ys is None):
         raise ValueError(f"conv2d out {tuple(out.shape)} / strides unsupported")
     rs = 0
     if residual is not None:
-        if residual.shape != out.shape:
-            raise ValueError(f"conv2d residual {tuple(residual.shape)} != {tuple(out.shape)}")
+        if tuple(residual.shape) != oshape:
+            raise ValueError(f"conv2d residual {tuple(residual.shape)} != {oshape}")
         rs = _pix_stride(residual)
         if rs is None:
             residual = residual.contiguous()
@@ -406,6 +480,9 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
     code = ACT[act]
 
     def run(tile, split, part=None):
+        nonlocal out
+        if out is None:  # norm without keep_raw, and the reduce does not apply it (or tuning.choose is timing plans)
+            out = torch.empty(oshape, dtype=torch.bfloat16, device=x.device)
         ws = _ws(split, M, Cout, x.device)
         _lib.call("csk_conv2d_ex", _p(out), _p(x), _p(wp), _p(bias), _p(bias2d), b2s, _p(residual),
                   B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, int(bool(up2x)), xs, ys, rs, code,
@@ -413,8 +490,8 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
 
     rs2 = 0
     if residual2 is not None:
-        if residual2.shape != out.shape:
-            raise ValueError(f"conv2d residual2 {tuple(residual2.shape)} != {tuple(out.shape)}")
+        if tuple(residual2.shape) != oshape:
+            raise ValueError(f"conv2d residual2 {tuple(residual2.shape)} != {oshape}")
         rs2 = _pix_stride(residual2)
         if rs2 is None:
             residual2 = residual2.contiguous()
@@ -435,7 +512,7 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
         _lib.call("csk_conv_tile2", _p(out), _p(x), _p(wp), _p(bias), _p(residual), _p(residual2), B, Ho, Wo, Cin,
                   Cout, xs, ys, rs, rs2, code, float(out_scale), float(res_scale), int(bool(up2x)), 0, _s())
         CONV_TILE_STATS[0] += 1
-        return out
+        return out  # never with a norm: it sets gn_stats, which this kernel does not produce
     if residual2 is not None or res_scale != 1.0:
         # the implicit GEMM's epilogue has one unscaled residual: conv into a
         # temporary, then one combining pass (residual2 is read before out is written)
@@ -447,12 +524,39 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
         out.copy_(y)
         return out
     tile, split = tuning.choose(key, M, Cout, K, run)
+    if norm is not None:
+        gamma, beta, groups, eps, silu, keep_raw = norm
+        if ys == Cout and _skgn_ok(split, K, M, Cout, Ho * Wo, ys, code, gamma, beta, groups, silu, bias, bias2d, b2s,
+                                   residual, rs, out, keep_raw):
+            yn = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
+            ws = _ws(split, M, Cout, x.device)
+            _lib.call("csk_conv2d_gn", _p(out) if keep_raw else None, _p(x), _p(wp), _p(bias), _p(bias2d), b2s,
+                      _p(residual), B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, int(bool(up2x)), xs, ys, rs,
+                      float(out_scale), int(dilation), tile, split, _p(ws), _p(yn), _p(gamma), _p(beta), int(groups),
+                      float(eps), int(bool(silu)), int(bool(keep_raw)), _s())
+            SKGN_STATS[0] += 1
+            if SKGN_SITES is not None:
+                SKGN_SITES.append((B, Ho, Wo, Cin, Cout, split, bool(keep_raw)))
+            return (yn, out) if keep_raw else yn
     seg = _gn_seg(tile, split, Ho * Wo, M, code, Cout) if gn_stats and ys == Cout else 0
     part = _gn_part(M, Cout, seg, x.device) if seg else None
     run(tile, split, part)
     if part is not None:
         out._csk_gn = (part, seg)
-    return out
+    return _norm_after(out, norm, norm_optional)
+
+
+def _norm_after(out, norm, optional=False):
+    """conv2d's ``norm`` argument where the conv kernel did not apply it"""
+    if norm is None:
+        return out
+    gamma, beta, groups, eps, silu, keep_raw = norm
+    if optional and keep_raw:
+        SKGN_STATS[2] += 1
+        return None, out
+    SKGN_STATS[1] += 1
+    yn = group_norm(out, gamma, beta, groups, eps, silu)
+    return (yn, out) if keep_raw else yn
 
 
 def _conv2d_u8(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, out, dilation, residual2,

@@ -244,44 +244,52 @@ static int launch(const GemmArgs& a0, int ksplit, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// f[q][0..7] += partials of splits [s0, s0 + U) at rows w[q] (split stride
-// `total` floats): all U * R * 2 loads issued before the first add
-template <int U, int R>
-__device__ __forceinline__ void add_splits(float (&f)[R][8], const float* const (&w)[R], size_t total, int s0) {
-  float4 lo[U][R], hi[U][R];
+// f[q][0..W-1] += partials of splits [s0, s0 + U) at rows w[q] (split stride
+// `total` floats; W = 8 or 4 columns per row): all U * R * W / 4 loads issued
+// before the first add
+template <int U, int R, int W>
+__device__ __forceinline__ void add_splits(float (&f)[R][W], const float* const (&w)[R], size_t total, int s0) {
+  constexpr int V = W / 4;
+  static_assert(W % 4 == 0, "float4 loads");
+  float4 x[U][R][V];
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
     for (int q = 0; q < R; ++q) {
       const float* p = w[q] + (size_t)(s0 + u) * total;
-      lo[u][q] = *reinterpret_cast<const float4*>(p);
-      hi[u][q] = *reinterpret_cast<const float4*>(p + 4);
+#pragma unroll
+      for (int v = 0; v < V; ++v) x[u][q][v] = *reinterpret_cast<const float4*>(p + 4 * v);
     }
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
-    for (int q = 0; q < R; ++q) {
-      f[q][0] += lo[u][q].x; f[q][1] += lo[u][q].y; f[q][2] += lo[u][q].z; f[q][3] += lo[u][q].w;
-      f[q][4] += hi[u][q].x; f[q][5] += hi[u][q].y; f[q][6] += hi[u][q].z; f[q][7] += hi[u][q].w;
-    }
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        f[q][4 * v] += x[u][q][v].x; f[q][4 * v + 1] += x[u][q][v].y;
+        f[q][4 * v + 2] += x[u][q][v].z; f[q][4 * v + 3] += x[u][q][v].w;
+      }
   // keep the loads together: under register pressure (the GN reduce) the
   // scheduler otherwise interleaves each load pair with its adds and waits
-  __builtin_amdgcn_sched_group_barrier(0x020, 2 * U * R, 0);  // VMEM reads
-  __builtin_amdgcn_sched_group_barrier(0x002, 8 * U * R, 0);  // VALU adds
+  __builtin_amdgcn_sched_group_barrier(0x020, V * U * R, 0);  // VMEM reads
+  __builtin_amdgcn_sched_group_barrier(0x002, W * U * R, 0);  // VALU adds
 }
 
-// sum of all ksplit partials, SU (1 / 4 / 8) splits per memory round trip
-template <int SU, int R>
-__device__ __forceinline__ void sum_splits(float (&f)[R][8], const float* const (&w)[R], size_t total, int ksplit) {
+// sum of all ksplit partials, SU (1 / 4 / 8) splits per memory round trip; every
+// element is 0 + split 0 + split 1 + ... in that order whatever SU, R and W are
+template <int SU, int R, int W>
+__device__ __forceinline__ void sum_splits(float (&f)[R][W], const float* const (&w)[R], size_t total, int ksplit) {
 #pragma unroll
   for (int q = 0; q < R; ++q)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[q][j] = 0.f;
+    for (int j = 0; j < W; ++j) f[q][j] = 0.f;
   int s = 0;
   if constexpr (SU >= 8)
     for (; s + 8 <= ksplit; s += 8) add_splits<8, R>(f, w, total, s);
   if constexpr (SU >= 4)
     for (; s + 4 <= ksplit; s += 4) add_splits<4, R>(f, w, total, s);
+  if constexpr (SU == 2)  // the fused GN reduce at >= 4 items per thread (register budget)
+    for (; s + 2 <= ksplit; s += 2) add_splits<2, R>(f, w, total, s);
   for (; s < ksplit; ++s) add_splits<1, R>(f, w, total, s);
 }
 
@@ -312,7 +320,7 @@ __global__ void splitk_reduce8_kernel(const GemmArgs a, int ksplit) {
     const int m = (int)(i / NV), n = (int)(i - (size_t)m * NV) * 8;
     const float* const w[1] = {a.ws + (size_t)m * N + n};
     float ff[1][8];
-    sum_splits<SU, 1>(ff, w, total, ksplit);
+    sum_splits<SU>(ff, w, total, ksplit);
     float f[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = ff[0][j];
@@ -359,7 +367,7 @@ __global__ __launch_bounds__(256) void splitk_reduce8_gn_kernel(const GemmArgs a
     const float* w[RPT];
 #pragma unroll
     for (int q = 0; q < RPT; ++q) w[q] = a.ws + (size_t)(blockIdx.x * SPLITK_GN_SEG + r0 + q * RPI) * N + n;
-    sum_splits<SU, RPT>(f, w, total, ksplit);
+    sum_splits<SU>(f, w, total, ksplit);
     float bb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) bb[j] = 0.f;
@@ -418,6 +426,174 @@ __global__ __launch_bounds__(256) void splitk_reduce8_gn_kernel(const GemmArgs a
     *reinterpret_cast<float2*>(a.gn_part + ((size_t)blockIdx.x * N + nc) * 2) = make_float2(mu, q);
 }
 
+// Split-K reduce fused with the GroupNorm (+ SiLU) apply that consumes its
+// output (a ResNet's conv1 -> norm2): the reduce above wrote bf16 and statistics
+// partials which gn_apply_cb_kernel read straight back.  Here a workgroup owns
+// ALL pixels of one sample for ONE group (the step's shapes: 8 samples x 32
+// groups = 256 workgroups = the CUs, ~164 KB of fp32 partials each at every
+// UNet level), keeps the finished fp32 values in registers, takes the group's
+// two-pass mean / variance inside the workgroup and stores the normalised bf16
+// directly: no statistics partials, no finalize, no apply launch, and no raw
+// tensor unless the caller keeps it (conv2: the residual stream).
+//   value   : sum_splits (the order of additions of the plain reduces, so the
+//             raw value is bit-identical), then bias / bias2d / out_scale / residual
+//   stats   : from the unrounded fp32 values (as splitk_reduce8_gn_kernel)
+//   output  : silu(bf16(value) * gamma * rstd + (beta - mean * gamma * rstd)),
+//             the arithmetic of gn_apply_cb_kernel on the bf16 it would have read
+// Thread t finishes items t, t + 1024, ... (item = 4 channels of one pixel;
+// IPT of them, <= 20 values, so 1024 threads stay under 128 VGPRs).  A group's
+// run per pixel is 80 B (C = 640) / 160 B (1280), so neighbouring groups share
+// cache lines: xcd_remap puts a sample's groups on one XCD, whose L2 then
+// fetches each line once.
+// With keep_raw the raw tensor carries no gn_part statistics: they are per
+// (64-row segment, channel), and here a channel's rows are spread over the whole
+// workgroup, so emitting them would take a second LDS reduction per channel.  A
+// conv whose raw output later feeds a concat GroupNorm (a skip connection) stays
+// on splitk_reduce8_gn_kernel instead (models/unet.py).
+constexpr int SKGN_T = 1024, SKGN_MAX_IPT = 5;  // 6 items spill at 128 VGPRs
+struct GnFuseArgs {
+  bf16_t* y;            // normalised output [M][N], contiguous
+  const bf16_t* gamma;  // [N]
+  const bf16_t* beta;   // [N]
+  int groups;
+  float eps;
+  int silu;
+  int keep_raw;  // also store the raw bf16 conv output to GemmArgs::C
+};
+
+__device__ __forceinline__ void unpack4(const uint2& v, float* f) {
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+}
+
+// sum of v over the workgroup, the same value in every thread (fixed order)
+__device__ __forceinline__ float skgn_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < SKGN_T / 64; ++i) s += red[i];
+  return s;
+}
+
+template <int IPT, int SU>
+__global__ __launch_bounds__(SKGN_T) void splitk_reduce_gn_apply_kernel(const GemmArgs a, const GnFuseArgs gn,
+                                                                        int ksplit) {
+  __shared__ float red[2][SKGN_T / 64];
+  const int N = a.N, P = a.rows_per_b, G = gn.groups, Cg = N / G, NV = Cg >> 2;
+  const size_t total = (size_t)a.M * N;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int b = wg / G, c_lo = (wg - b * G) * Cg;
+  const int items = P * NV;
+  float f[IPT][4];
+  const float* w[IPT];
+  int m[IPT], c[IPT];
+  bool ok[IPT];
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int i = threadIdx.x + k * SKGN_T;
+    ok[k] = i < items;
+    const int ii = ok[k] ? i : 0;  // idle slots re-read item 0 and store nothing
+    const int p = ii / NV;
+    m[k] = b * P + p;
+    c[k] = c_lo + (ii - p * NV) * 4;
+    CSK_DCHECK(m[k] < a.M && c[k] + 4 <= N, SITE_SKGN, (long long)m[k] * N + c[k], total);
+    w[k] = a.ws + (size_t)m[k] * N + c[k];
+  }
+  sum_splits<SU>(f, w, total, ksplit);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    float t[4];
+    if (a.bias) {
+      unpack4(*reinterpret_cast<const uint2*>(a.bias + c[k]), t);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[k][j] += t[j];
+    }
+    if (a.bias2d) {
+      unpack4(*reinterpret_cast<const uint2*>(a.bias2d + (size_t)b * a.ldb2 + c[k]), t);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[k][j] += t[j];
+    }
+    if (a.out_scale != 1.0f) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[k][j] *= a.out_scale;
+    }
+    if (a.res) {
+      unpack4(*reinterpret_cast<const uint2*>(a.res + (size_t)m[k] * a.ldr + c[k]), t);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[k][j] += t[j];
+    }
+    if (ok[k]) s += (f[k][0] + f[k][1]) + (f[k][2] + f[k][3]);
+  }
+  const float cnt = (float)items * 4.0f;
+  const float mean = skgn_block_sum(s, red[0]) / cnt;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    if (ok[k]) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = f[k][j] - mean;
+        q += d * d;
+      }
+    }
+  }
+  const float rstd = rsqrtf(skgn_block_sum(q, red[1]) / fmaxf(cnt, 1.f) + gn.eps);
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    if (!ok[k]) continue;
+    const uint2 raw = make_uint2(pack2(f[k][0], f[k][1]), pack2(f[k][2], f[k][3]));
+    if (gn.keep_raw) *reinterpret_cast<uint2*>(a.C + (size_t)m[k] * a.ldc + c[k]) = raw;
+    float x[4], gf[4], bf[4];
+    unpack4(raw, x);
+    unpack4(*reinterpret_cast<const uint2*>(gn.gamma + c[k]), gf);
+    unpack4(*reinterpret_cast<const uint2*>(gn.beta + c[k]), bf);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sa = gf[j] * rstd;
+      const float t = x[j] * sa + (bf[j] - mean * sa);
+      x[j] = gn.silu ? silu_f(t) : t;
+    }
+    *reinterpret_cast<uint2*>(gn.y + (size_t)m[k] * N + c[k]) = make_uint2(pack2(x[0], x[1]), pack2(x[2], x[3]));
+  }
+}
+
+// runtime switch of the fused reduce + GroupNorm apply (tools/abstep.py skgnf0 /
+// skgnf1, and the tests' unfused comparison); off: csk_splitk_gn_fused_ok() == 0
+static int g_skgn_fused = 1;
+CSK_API int csk_set_skgn_fused(int v) {
+  g_skgn_fused = v;
+  return 0;
+}
+
+// items per thread of the fused kernel for this output, 0: not eligible (whole
+// groups of 4-channel vectors, one sample's group within the register budget)
+static int skgn_ipt(int M, int N, int rows_per_b, int groups) {
+  if (groups <= 0 || rows_per_b <= 0 || N % groups || M % rows_per_b || (N / groups) % 4) return 0;
+  const long long items = (long long)rows_per_b * (N / groups / 4);
+  const long long ipt = (items + SKGN_T - 1) / SKGN_T;
+  return ipt <= SKGN_MAX_IPT ? (int)ipt : 0;
+}
+// One workgroup per (sample, group) needs enough of them: at CFG batch 2 (64
+// workgroups, each pulling up to 16 splits of its group through one CU) the fused
+// kernel cost the step +0.02 ms, at batch 8 (256) it saves 0.14 ms
+// and at batch 4 (128) 0.09 ms (profiles/r8-abstep.txt); below this grid the host keeps
+// the reduce and the apply as two full-width kernels (tools/abstep.py skgnw<N>).
+// The floor comes from whole-step A/Bs of the SD2.1 UNet at CFG batch 2 / 4 / 8
+// only: no site was timed on its own, and the other ResnetBlock2D users (SDXL,
+// ControlNet, the VAE) inherit it unmeasured.
+static int g_skgn_min_wg = 128;
+CSK_API int csk_set_skgn_min_wg(int v) {
+  g_skgn_min_wg = v;
+  return 0;
+}
+CSK_API int csk_get_skgn_min_wg() { return g_skgn_min_wg; }
+CSK_API int csk_splitk_gn_fused_ok(int M, int N, int rows_per_b, int groups) {
+  return g_skgn_fused && skgn_ipt(M, N, rows_per_b, groups) > 0 && (M / rows_per_b) * groups >= g_skgn_min_wg;
+}
+
 // splits loaded per memory round trip in the split-K reduces (1: the old
 // one-split-at-a-time loop; A/B knob for tools/abstep.py skr1 / skr4 / skr8)
 static int g_skr_unroll = 4;  // 4: -0.022 ms (CFG 8) / -0.023 ms (CFG 2) per step vs 1; 8 no better (profiles/unet_step_ab_skr_r7d.txt)
@@ -425,8 +601,39 @@ CSK_API int csk_set_skr_unroll(int v) {
   g_skr_unroll = v;
   return 0;
 }
+CSK_API int csk_get_skr_unroll() { return g_skr_unroll; }
 
-static int splitk_reduce(const GemmArgs& a, int ksplit, hipStream_t s) {
+template <int IPT>
+static void launch_skgn(const GemmArgs& a, const GnFuseArgs& gn, int ksplit, int grid, hipStream_t s) {
+  // SU * IPT float4 are in flight beside the IPT * 4 sums: 4 splits per round trip
+  // fit the 128-VGPR budget up to 3 items per thread, 2 above (5 items spilled at 4)
+  constexpr int SU = IPT <= 3 ? 4 : 2;
+  if (g_skr_unroll >= 4) splitk_reduce_gn_apply_kernel<IPT, SU><<<grid, SKGN_T, 0, s>>>(a, gn, ksplit);
+  else splitk_reduce_gn_apply_kernel<IPT, 1><<<grid, SKGN_T, 0, s>>>(a, gn, ksplit);
+}
+
+// the fused reduce + GroupNorm apply; the host asked csk_splitk_gn_fused_ok()
+// first, so anything it cannot take is an error, not a fallback
+static int splitk_reduce_gn_apply(const GemmArgs& a, const GnFuseArgs& gn, int ksplit, hipStream_t s) {
+  const int ipt = g_skgn_fused ? skgn_ipt(a.M, a.N, a.rows_per_b, gn.groups) : 0;
+  auto al8 = [](const void* p) { return (size_t)p % 8 == 0; };
+  if (!ipt || a.act != ACT_NONE || a.gn_part || !gn.y || !gn.gamma || !gn.beta || (gn.keep_raw && !a.C) ||
+      (gn.keep_raw && a.ldc % 4) || (a.res && a.ldr % 4) || (a.bias2d && a.ldb2 % 4) || !al8(a.C) || !al8(a.res) ||
+      !al8(a.bias) || !al8(a.bias2d) || !al8(gn.y) || !al8(gn.gamma) || !al8(gn.beta) || (size_t)a.ws % 16)
+    return (int)hipErrorInvalidValue;
+  const int grid = (a.M / a.rows_per_b) * gn.groups;
+  switch (ipt) {
+    case 1: launch_skgn<1>(a, gn, ksplit, grid, s); break;
+    case 2: launch_skgn<2>(a, gn, ksplit, grid, s); break;
+    case 3: launch_skgn<3>(a, gn, ksplit, grid, s); break;
+    case 4: launch_skgn<4>(a, gn, ksplit, grid, s); break;
+    default: launch_skgn<SKGN_MAX_IPT>(a, gn, ksplit, grid, s); break;
+  }
+  return (int)hipGetLastError();
+}
+
+static int splitk_reduce(const GemmArgs& a, int ksplit, hipStream_t s, const GnFuseArgs* gn = nullptr) {
+  if (gn) return splitk_reduce_gn_apply(a, *gn, ksplit, s);
   const size_t total = (size_t)a.M * a.N;
   const bool vec = a.N % 8 == 0 && a.ldc % 8 == 0 && (!a.res || a.ldr % 8 == 0) && (!a.bias2d || a.ldb2 % 8 == 0) &&
                    ((size_t)a.C % 16 == 0) && (!a.res || (size_t)a.res % 16 == 0) && (!a.bias || (size_t)a.bias % 16 == 0) &&
@@ -479,7 +686,7 @@ CSK_API int csk_set_gn_lds(int v) {
 static inline bool glds_tile(int t) { return (t >= 11 && t <= 29) || t == 36; }
 
 template <bool CONV>
-static int dispatch(GemmArgs a, int tile, int ksplit, hipStream_t s) {
+static int dispatch(GemmArgs a, int tile, int ksplit, hipStream_t s, const GnFuseArgs* gn = nullptr) {
   a.zero = csk_zero_ptr();
   a.gn_lds = g_gn_lds;
   a.sw_odd = g_sw_odd;
@@ -513,6 +720,9 @@ static int dispatch(GemmArgs a, int tile, int ksplit, hipStream_t s) {
     a.kchunk = a.K;
     ksplit = 1;
   }
+  // the fused GroupNorm apply lives in the reduce kernel: the host mirrors the
+  // effective split above (hip_ops._eff_split) and asks for it only when > 1
+  if (gn && (fixup || ksplit == 1)) return (int)hipErrorInvalidValue;
   if (fixup && ksplit > 1) {  // gemm_glds.hip launch_glds: per-tile counters, no reduce kernel
     a.fx_ws = a.ws;
     const int err = csk_gemm_glds_launch(a, tile, ksplit, CONV, s);
@@ -561,7 +771,7 @@ static int dispatch(GemmArgs a, int tile, int ksplit, hipStream_t s) {
   }
   if (err || ksplit == 1) return err;
   if (a.gn_part) a.gn_seg = SPLITK_GN_SEG;  // mirrored by hip_ops._gn_seg
-  return splitk_reduce(a, ksplit, s);
+  return splitk_reduce(a, ksplit, s, gn);
 }
 
 // y[M, ldc] = act(A[M, lda] . W[N, ldb]^T + bias + bias2d) * out_scale + res[M, ldr]
@@ -690,10 +900,10 @@ CSK_API int csk_gemm(void* C, const void* A, const void* W, const void* bias, co
 // buffers (>= channel counts: lets dense blocks read and write channel slices of
 // one concat buffer without copies).
 // b2s: row stride of bias2d ([B][b2s], 0 -> Cout)
-CSK_API int csk_conv2d_ex(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
-                          const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
-                          int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, int act, float out_scale, int dil,
-                          void* gn_part, int tile, int ksplit, void* ws, hipStream_t stream) {
+static int conv2d_impl(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
+                       const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
+                       int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, int act, float out_scale, int dil,
+                       void* gn_part, int tile, int ksplit, void* ws, hipStream_t stream, const GnFuseArgs* gn) {
   if (Cin % 8 != 0 || xs % 8 != 0 || xs < Cin || (b2s != 0 && b2s < Cout)) return (int)hipErrorInvalidValue;
   GemmArgs a{};
   a.A = (const bf16_t*)X; a.W = (const bf16_t*)Wp; a.C = (bf16_t*)Y;
@@ -710,7 +920,36 @@ CSK_API int csk_conv2d_ex(void* Y, const void* X, const void* Wp, const void* bi
   a.a_end = a.A + ((size_t)B * H * W - 1) * xs + Cin;
   a.w_end = a.W + (size_t)(Cout - 1) * a.ldb + a.K;
   if (a.M == 0) return 0;
-  return dispatch<true>(a, tile, ksplit, stream);
+  if (!Y || !X || !Wp) return (int)hipErrorInvalidValue;  // (an empty tensor's pointer may be null: M == 0 above)
+  return dispatch<true>(a, tile, ksplit, stream, gn);
+}
+
+CSK_API int csk_conv2d_ex(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
+                          const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
+                          int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, int act, float out_scale, int dil,
+                          void* gn_part, int tile, int ksplit, void* ws, hipStream_t stream) {
+  return conv2d_impl(Y, X, Wp, bias, bias2d, b2s, res, B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, up2x, xs, ys,
+                     rs, act, out_scale, dil, gn_part, tile, ksplit, ws, stream, nullptr);
+}
+
+// csk_conv2d_ex of a split-K plan (ksplit > 1, no activation) whose reduce also
+// applies the GroupNorm (+ SiLU) that consumes the output
+// (splitk_reduce_gn_apply_kernel): Yn [B][Ho][Wo][Cout] contiguous gets the
+// normalised tensor, Y (pixel stride ys) the raw conv output when keep_raw
+// (else it may be null).  Ask csk_splitk_gn_fused_ok() first.
+CSK_API int csk_conv2d_gn(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
+                          const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
+                          int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, float out_scale, int dil, int tile,
+                          int ksplit, void* ws, void* Yn, const void* gamma, const void* beta, int groups, float eps,
+                          int silu, int keep_raw, hipStream_t stream) {
+  if (ksplit <= 1 || !ws || !Yn || (keep_raw && !Y)) return (int)hipErrorInvalidValue;
+  GnFuseArgs gn{};
+  gn.y = (bf16_t*)Yn; gn.gamma = (const bf16_t*)gamma; gn.beta = (const bf16_t*)beta;
+  gn.groups = groups; gn.eps = eps; gn.silu = silu; gn.keep_raw = keep_raw;
+  // without keep_raw nothing stores through C: the split kernels write the workspace only
+  return conv2d_impl(keep_raw ? Y : Yn, X, Wp, bias, bias2d, b2s, res, B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho,
+                     Wo, up2x, xs, keep_raw ? ys : Cout, rs, ACT_NONE, out_scale, dil, nullptr, tile, ksplit, ws, stream,
+                     &gn);
 }
 
 CSK_API int csk_conv2d(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, const void* res,

@@ -132,7 +132,8 @@ struct GemmArgs {
 
 // Debug-check sites (CSK_DEBUG record field 1); +100: the LDS destination
 enum DmaSite { SITE_GLDS_A = 1, SITE_GLDS_B, SITE_PERSIST_A, SITE_PERSIST_B,
-               SITE_8P_A, SITE_8P_B, SITE_8R_A, SITE_8R_B, SITE_WIDE_KV };
+               SITE_8P_A, SITE_8P_B, SITE_8R_A, SITE_8R_B, SITE_WIDE_KV,
+               SITE_SKGN };  // fused split-K reduce + GroupNorm apply: (row, column) inside [M][N]
 
 typedef __attribute__((address_space(1))) const void* csk_gptr_t;
 typedef __attribute__((address_space(3))) void* csk_lptr_t;

@@ -12,6 +12,7 @@ _os.environ.setdefault("SDAAS_ALLOW_RANDOM", "1")
 _os.environ.setdefault("SDAAS_OFFLINE", "1")
 
 import argparse
+import collections
 import os
 import statistics
 import sys
@@ -60,6 +61,10 @@ def apply_arm(arm):
         _lib.call("csk_set_short_kv_variant", int(arm[3:]))
     elif arm.startswith("attn"):
         hip_ops.ATTN_VARIANT = int(arm[4:])
+    elif arm in ("skgnf0", "skgnf1"):  # split-K reduce + GroupNorm apply: two kernels (0) / one fused kernel (1)
+        hip_ops.set_skgn_fused(arm == "skgnf1")
+    elif arm.startswith("skgnw"):  # fused reduce + GroupNorm apply: smallest grid (samples x groups) it takes
+        hip_ops.set_skgn_min_wg(int(arm[5:]))
     elif arm in ("skgn0", "skgn1"):
         hip_ops.SPLITK_GN = arm == "skgn1"
     elif arm.startswith("skr"):  # split-K reduces: partial splits loaded per memory round trip (1 / 4 / 8)
@@ -109,9 +114,20 @@ def main():
     kv = p.unet.encode_context(ctx)
     graphs = {}
     for arm in a.arms.split(","):
-        for sub in arm.split("+"):  # combined knobs, e.g. gcm2+gcb1024 (settings persist into later arms)
+        # combined knobs, e.g. gcm2+gcb1024 (settings persist into later arms); "arm@tag"
+        # repeats an arm under another name: the spread between identical arms
+        for sub in arm.split("@")[0].split("+"):
             apply_arm(sub)
-        graphs[arm] = _UNetGraph(p.unet, x, kv, None, cfg_dup=arm != "dup0" and not a.no_cfg)
+        hip_ops.SKGN_SITES = []
+        warmup = 2
+        graphs[arm] = _UNetGraph(p.unet, x, kv, None, warmup=warmup, cfg_dup=arm != "dup0" and not a.no_cfg)
+        n = len(hip_ops.SKGN_SITES) // (warmup + 1)  # every forward fuses the same sites; the last one is the captured
+        if n:
+            sites = collections.Counter(hip_ops.SKGN_SITES[-n:])
+            print(f"{arm:10s} fused reduce + GroupNorm sites per forward: {n}", flush=True)
+            for (b, h, w, ci, co, sp, raw), k in sorted(sites.items()):
+                print(f"    {k} x conv {b}x{h}x{w} {ci} -> {co} split {sp} {'conv2 (raw kept)' if raw else 'conv1'}", flush=True)
+        hip_ops.SKGN_SITES = None
     res = {arm: [] for arm in graphs}
     for _ in range(a.rounds):
         for arm, g in graphs.items():

@@ -34,6 +34,11 @@ def flops_of(name, a):
         Ho, Wo, up = a[17], a[18], a[19]
         return (f"conv B{B} {H}x{W}{' up2x' if up else ''} s{stride} {Cin}->{Cout} k{kh}",
                 2.0 * B * Ho * Wo * Cout * kh * kw * Cin, a[-4])
+    if name == "csk_conv2d_gn":  # split-K conv whose reduce applies the following GroupNorm (gemm.hip)
+        B, H, W, Cin, Cout, kh, kw, stride = a[7:15]
+        Ho, Wo, up = a[17], a[18], a[19]
+        return (f"conv+gn B{B} {H}x{W}{' up2x' if up else ''} s{stride} {Cin}->{Cout} k{kh}{' +raw' if a[34] else ''}",
+                2.0 * B * Ho * Wo * Cout * kh * kw * Cin, a[25])
     if name == "csk_attention":
         B, H, Sq, Skv, D = a[5:10]
         return f"attn B{B} H{H} Sq{Sq} Skv{Skv} D{D}", 4.0 * B * H * Sq * Skv * D, None
