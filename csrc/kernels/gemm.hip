@@ -715,7 +715,10 @@ static int dispatch(GemmArgs a, int tile, int ksplit, hipStream_t s, const GnFus
     const int nk = (a.K + BK - 1) / BK;
     a.kchunk = ((nk + ksplit - 1) / ksplit) * BK;
     ksplit = (a.K + a.kchunk - 1) / a.kchunk;
-  } else {
+  }
+  // (also a requested split that collapses to one, K <= 64: with the workspace
+  // left set the kernels wrote fp32 partials that no reduce picked up)
+  if (ksplit <= 1) {
     a.ws = nullptr;
     a.kchunk = a.K;
     ksplit = 1;

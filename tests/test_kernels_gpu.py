@@ -9,6 +9,7 @@ import torch.nn.functional as F
 from chiaswarm_amd import ops
 from chiaswarm_amd.ops import hip_ops
 from chiaswarm_amd.schedulers import StepCoeffs
+from tests._numerics import assert_bf16_close, conv_ref64
 
 pytestmark = pytest.mark.gpu
 
@@ -47,17 +48,37 @@ def test_gemm_conv_every_tile_and_splitk(gpu, tile, split):
               _p(ws), _s())
     ref = ops._ref_gemm(a.float().cpu(), w.float().cpu(), b.float().cpu(), r.float().cpu(), "silu")
     assert rel_err(out.cpu(), ref) < 1e-2
-    # implicit-GEMM conv, K split across taps
-    B, H, W, Cin, Cout = 2, 10, 12, 96, 48
-    x = rnd(B, H, W, Cin, dev=gpu)
-    wp = ops.pack_conv_weight(rnd(Cout, Cin, 3, 3, dev=gpu, scale=(9 * Cin) ** -0.5))
-    b2 = rnd(B, Cout, dev=gpu)
-    y = torch.empty(B, H, W, Cout, dtype=torch.bfloat16, device=gpu)
-    ws = torch.empty(split * B * H * W * Cout, dtype=torch.float32, device=gpu)
-    _lib.call("csk_conv2d", _p(y), _p(x), _p(wp), None, _p(b2), None, B, H, W, Cin, Cout, 3, 3, 1, 1, 1, H, W, 0,
-              Cin, Cout, 0, 0, 1.0, 1, None, tile, split, _p(ws), _s())
-    ref = ops._ref_conv2d(x.float().cpu(), wp.float().cpu(), None, 1, 1, None, False, b2.float().cpu())
-    assert rel_err(y.cpu(), ref) < 1e-2
+    # implicit-GEMM conv, K split across taps: Cin = 96 takes every tile's guarded
+    # staging (a tap boundary inside a K-step), Cin = 64 its FAST staging
+    B, H, W, Cout = 2, 10, 12, 48
+    for Cin in (96, 64):
+        x = rnd(B, H, W, Cin, dev=gpu)
+        wp = ops.pack_conv_weight(rnd(Cout, Cin, 3, 3, dev=gpu, scale=(9 * Cin) ** -0.5))
+        b2 = rnd(B, Cout, dev=gpu)
+        y = torch.empty(B, H, W, Cout, dtype=torch.bfloat16, device=gpu)
+        ws = torch.empty(split * B * H * W * Cout, dtype=torch.float32, device=gpu)
+        _lib.call("csk_conv2d", _p(y), _p(x), _p(wp), None, _p(b2), None, B, H, W, Cin, Cout, 3, 3, 1, 1, 1, H, W, 0,
+                  Cin, Cout, 0, 0, 1.0, 1, None, tile, split, _p(ws), _s())
+        ref = ops._ref_conv2d(x.float().cpu(), wp.float().cpu(), None, 1, 1, None, False, b2.float().cpu())
+        assert rel_err(y.cpu(), ref) < 1e-2, Cin
+        ref64, S = conv_ref64(x, wp, None, 1, 1, False, b2)
+        assert_bf16_close(y, ref64, S, 9 * Cin, f"tile {tile} split {split} Cin={Cin}")
+
+
+@pytest.mark.parametrize("tile,split", [(4, 3), (14, 3), (14, -3), (31, 3)])  # -3: the LDS-DMA tiles' in-kernel fixup
+def test_gemm_split_collapsing_to_one_k_step(gpu, tile, split):
+    """K = 64 is one K-step: a requested split runs unsplit and must still write
+    the output (it wrote workspace partials that no reduce consumed)."""
+    from chiaswarm_amd.ops import _lib
+    from chiaswarm_amd.ops.hip_ops import _p, _s, _ws
+
+    M, N, K = 200, 96, 64
+    a, w, b, r = rnd(M, K, dev=gpu), rnd(N, K, dev=gpu, scale=K ** -0.5), rnd(N, dev=gpu), rnd(M, N, dev=gpu)
+    out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=gpu)
+    _lib.call("csk_gemm", _p(out), _p(a), _p(w), _p(b), None, _p(r), M, N, K, K, K, N, N, 1, 0, 1.0, None, tile, split,
+              _p(_ws(split, M, N, gpu)), _s())
+    ref = ops._ref_gemm(a.float().cpu(), w.float().cpu(), b.float().cpu(), r.float().cpu(), None)
+    assert rel_err(out.cpu(), ref) < 1e-2
 
 
 def test_gemm_strided_a_and_geglu(gpu):
@@ -612,6 +633,8 @@ def test_phased_256_tiles_gemm_conv(gpu, tile, split):
                   Wo, up, Cin, Cout, 0, 0, 1.0, 1, None, tile, split, _p(ws), _s())
         ref = ops._ref_conv2d(x.float().cpu(), wp.float().cpu(), None, stride, 1, None, bool(up), b2.float().cpu())
         assert rel_err(y.cpu(), ref) < 1e-2, (B, H, W, Cin, Cout, stride, up)
+        ref64, S = conv_ref64(x, wp, None, stride, 1, bool(up), b2)
+        assert_bf16_close(y, ref64, S, 9 * Cin, f"tile {tile} split {split} {(B, H, W, Cin, Cout, stride, up)}")
 
 
 @pytest.mark.parametrize("tile", [31, 32, 33, 34])
