@@ -19,7 +19,11 @@ offline) and says so in the log.
 
 Each detector is built once per process, kept resident on the GPU (bf16 there,
 fp32 on CPU) and runs as plain PyTorch modules: these run once per job on one
-image, far off the denoising hot path.
+image, far off the denoising hot path.  The exception is the ConvNeXt backbone
+of ``seg``: on the HIP path the blocks of a stage run back to back in NHWC bf16
+on the native ops (depthwise 7x7 kernel, LayerNorm, the MFMA GEMMs with GELU and
+with the layer scale + residual folded into ``pwconv2``); its CPU and
+``reference``-mode paths are the plain modules.
 """
 from __future__ import annotations
 
@@ -32,6 +36,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from PIL import Image
+
+from .. import ops
 
 _CACHE: dict = {}
 _FILES = {
@@ -768,6 +774,31 @@ class _CNBlock(nn.Module):
         h = self.pwconv2(F.gelu(self.pwconv1(self.layernorm(h)))) * self.layer_scale_parameter
         return x + h.permute(0, 3, 1, 2)
 
+    def _native(self):
+        """Weights of the NHWC path: the packed fp32 depthwise filter and
+        ``pwconv2`` with ``layer_scale_parameter`` folded into its rows and bias
+        (rebuilt when a source tensor moves or is written)."""
+        srcs = (self.dwconv.weight, self.pwconv2.weight, self.pwconv2.bias, self.layer_scale_parameter)
+        key = tuple((t.device, t.dtype, t._version) for t in srcs)
+        if getattr(self, "_nat_key", None) != key:
+            g = self.layer_scale_parameter.detach().float()
+            w2 = self.pwconv2.weight.detach()
+            self._nat = (ops.pack_depthwise_weight(self.dwconv.weight),
+                         (w2.float() * g[:, None]).to(w2.dtype).contiguous(),
+                         (self.pwconv2.bias.detach().float() * g).to(w2.dtype))
+            self._nat_key = key
+        return self._nat
+
+    def forward_nhwc(self, x):
+        """The block on an NHWC bf16 map through the HIP ops: depthwise 7x7,
+        LayerNorm, pwconv1 + GELU, pwconv2 (layer scale folded) + the residual
+        in its epilogue."""
+        wp, w2, b2 = self._native()
+        h = ops.depthwise_conv2d(x, wp, self.dwconv.bias, stride=1, padding=3)
+        h = ops.layer_norm(h, self.layernorm.weight, self.layernorm.bias, self.layernorm.eps)
+        h = ops.gemm(h, self.pwconv1.weight, self.pwconv1.bias, act="gelu")
+        return ops.gemm(h, w2, b2, residual=x)
+
 
 class _CNStage(nn.Module):
     def __init__(self, cin, c, depth, down):
@@ -776,7 +807,14 @@ class _CNStage(nn.Module):
         self.layers = nn.Sequential(*[_CNBlock(c) for _ in range(depth)])
 
     def forward(self, x):
-        return self.layers(self.downsampling_layer(x))
+        h = self.downsampling_layer(x)
+        if ops.use_hip(h) and h.dtype == torch.bfloat16:
+            # the stage's blocks back to back in NHWC on the HIP ops; layout converts here only
+            h = h.permute(0, 2, 3, 1).contiguous()
+            for blk in self.layers:
+                h = blk.forward_nhwc(h)
+            return h.permute(0, 3, 1, 2)
+        return self.layers(h)
 
 
 class _CNEmb(nn.Module):

@@ -46,7 +46,6 @@ from typing import Sequence
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
 from .layers import Attention, Conv2d, LayerNorm, Linear, Prepared
@@ -154,35 +153,46 @@ def _binomial_kernel(c, scale=1.0):
     return (k1[:, None] * k1[None, :]).expand(c, 1, 4, 4).contiguous()
 
 
-class KDownsample2D(nn.Module):
-    """Depthwise [1,3,3,1]/8 binomial filter, reflect pad 1, stride 2 (no
-    checkpoint params; the filter is a non-persistent buffer so it moves with
-    the model and never needs a host copy inside a captured graph).  A fixed
-    16-tap depthwise filter: MIOpen's grouped conv, not worth an MFMA tile."""
+class _KResample2D(Prepared):
+    """Fixed depthwise binomial filter.  ``kernel`` [C, 1, 4, 4] is a
+    non-persistent buffer (no checkpoint params; it moves with the model);
+    ``wp`` is its packed fp32 [4, 4, C] copy for ``ops.depthwise_*``, built by
+    ``prepare()`` or at first use, so a captured graph never copies from the host."""
+
+    def __init__(self, channels, scale):
+        super().__init__()
+        self.register_buffer("kernel", _binomial_kernel(channels, scale), persistent=False)
+
+    def prepare(self):
+        self.wp = ops.pack_depthwise_weight(self.kernel)
+
+    def _wp(self):
+        wp = getattr(self, "wp", None)
+        if wp is None or wp.device != self.kernel.device:
+            self.prepare()
+        return self.wp
+
+
+class KDownsample2D(_KResample2D):
+    """Depthwise [1,3,3,1]/8 binomial filter, reflect pad 1, stride 2: one
+    launch of the NHWC depthwise kernel on the HIP path (no layout round trip)."""
 
     def __init__(self, channels):
-        super().__init__()
-        self.register_buffer("kernel", _binomial_kernel(channels), persistent=False)
+        super().__init__(channels, 1.0)
 
     def forward(self, x):
-        c = x.shape[-1]
-        xn = F.pad(x.permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect")
-        y = F.conv2d(xn, self.kernel.to(x.dtype), stride=2, groups=c)
-        return y.permute(0, 2, 3, 1).contiguous()
+        return ops.depthwise_conv2d(x, self._wp(), stride=2, padding=1, pad_mode="reflect")
 
 
-class KUpsample2D(nn.Module):
-    """Transposed depthwise binomial filter (x2 gain), reflect pad 1, stride 2."""
+class KUpsample2D(_KResample2D):
+    """Transposed depthwise binomial filter (x2 gain), reflect pad 1, stride 2,
+    crop 3: the gather form of the same kernel."""
 
     def __init__(self, channels):
-        super().__init__()
-        self.register_buffer("kernel", _binomial_kernel(channels, 2.0), persistent=False)
+        super().__init__(channels, 2.0)
 
     def forward(self, x):
-        c = x.shape[-1]
-        xn = F.pad(x.permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect")
-        y = F.conv_transpose2d(xn, self.kernel.to(x.dtype), stride=2, padding=3, groups=c)
-        return y.permute(0, 2, 3, 1).contiguous()
+        return ops.depthwise_conv_transpose2d(x, self._wp(), in_padding=1, pad_mode="reflect", crop=3)
 
 
 class KTimestepEmbedding(nn.Module):

@@ -579,6 +579,141 @@ def conv2d(x, wp, bias=None, stride=1, padding=1, residual=None, up2x=False, bia
 
 
 # ----------------------------------------------------------------------------
+# Depthwise conv2d NHWC (K-UNet binomial resamplers, ConvNeXt 7x7)
+# ----------------------------------------------------------------------------
+DW_KMAX = 7  # largest depthwise kernel side (csrc/kernels/dwconv.hip DW_KMAX)
+DW_PAD_MODES = ("zeros", "reflect")
+
+
+def pack_depthwise_weight(w: torch.Tensor) -> torch.Tensor:
+    """[C, 1, kh, kw] (PyTorch depthwise) or [C, kh, kw] -> fp32 [kh, kw, C]."""
+    if w.dim() == 4:
+        if w.shape[1] != 1:
+            raise ValueError(f"pack_depthwise_weight: expected [C, 1, kh, kw], got {tuple(w.shape)}")
+        w = w[:, 0]
+    if w.dim() != 3:
+        raise ValueError(f"pack_depthwise_weight: expected [C, 1, kh, kw] or [C, kh, kw], got {tuple(w.shape)}")
+    return w.detach().permute(1, 2, 0).float().contiguous()
+
+
+def _dw_check(name, x, wp, bias, padding, pad_mode):
+    """Validation shared by the reference and the HIP path of the depthwise ops;
+    returns (pt, pl, pb, pr)."""
+    if x.dim() != 4:
+        raise ValueError(f"{name}: x must be NHWC [B, H, W, C], got {tuple(x.shape)}")
+    B, H, W, C = x.shape
+    if C % 8 != 0:
+        raise ValueError(f"{name}: C = {C} is not a multiple of 8")
+    if wp.dim() != 3 or wp.shape[2] != C or wp.dtype != torch.float32:
+        raise ValueError(f"{name}: wp must be pack_depthwise_weight's fp32 [kh, kw, {C}], got "
+                         f"{wp.dtype} {tuple(wp.shape)}")
+    kh, kw = wp.shape[0], wp.shape[1]
+    if not (1 <= kh <= DW_KMAX and 1 <= kw <= DW_KMAX):
+        raise ValueError(f"{name}: kernel {kh}x{kw} outside 1..{DW_KMAX}")
+    if pad_mode not in DW_PAD_MODES:
+        raise ValueError(f"{name}: pad_mode {pad_mode!r} not in {DW_PAD_MODES}")
+    pad = norm_padding(padding)
+    if min(pad) < 0:
+        raise ValueError(f"{name}: negative padding {pad}")
+    pt, pl, pb, pr = pad
+    if pad_mode == "reflect" and (max(pt, pb) >= H or max(pl, pr) >= W):
+        raise ValueError(f"{name}: reflect padding {pad} must be smaller than the input {H}x{W}")
+    if bias is not None and tuple(bias.shape) != (C,):
+        raise ValueError(f"{name}: bias shape {tuple(bias.shape)} != ({C},)")
+    return pad
+
+
+def _dw_view_check(name, t, shape, what):
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what} shape {tuple(t.shape)} != {tuple(shape)}")
+
+
+def _dw_padded(x, pad, pad_mode):
+    """NCHW view of NHWC ``x`` in the reference compute dtype, explicitly padded."""
+    pt, pl, pb, pr = pad
+    xn = x.to(_cdt(x)).permute(0, 3, 1, 2)
+    if max(pad) == 0:
+        return xn
+    return F.pad(xn, (pl, pr, pt, pb), mode="reflect" if pad_mode == "reflect" else "constant")
+
+
+def _ref_depthwise_conv2d(x, wp, bias, stride, pad, pad_mode, residual):
+    dt = _cdt(x)
+    c = x.shape[-1]
+    w = wp.permute(2, 0, 1).unsqueeze(1).to(dt).contiguous()  # [C, 1, kh, kw]
+    y = F.conv2d(_dw_padded(x, pad, pad_mode), w, bias.to(dt) if bias is not None else None, stride=stride, groups=c)
+    y = y.permute(0, 2, 3, 1)
+    if residual is not None:
+        y = y + residual.to(dt)
+    return y.to(x.dtype).contiguous()
+
+
+def depthwise_conv2d(x, wp, bias=None, stride=1, padding=0, pad_mode="zeros", residual=None, out=None):
+    """Depthwise NHWC conv: y[b, oh, ow, c] = bias[c] + sum_ij wp[i, j, c] *
+    xp[b, oh*s + i, ow*s + j, c] (+ residual), ``xp`` = ``x`` padded by
+    ``padding`` (int or (top, left, bottom, right)) with zeros or by reflection
+    (``F.pad(mode="reflect")``).  ``wp``: ``pack_depthwise_weight`` fp32
+    [kh, kw, C], kh, kw <= 7; stride 1 or 2; C % 8 == 0.  ``x``, ``residual``
+    and ``out`` may be channel slices of wider NHWC buffers."""
+    name = "depthwise_conv2d"
+    pad = _dw_check(name, x, wp, bias, padding, pad_mode)
+    if stride not in (1, 2):
+        raise ValueError(f"{name}: stride {stride} not in (1, 2)")
+    B, H, W, C = x.shape
+    ho, wo = conv_out_size(H, W, wp.shape[0], wp.shape[1], stride, pad)
+    if ho < 1 or wo < 1:
+        raise ValueError(f"{name}: kernel {wp.shape[0]}x{wp.shape[1]} larger than the padded input")
+    _dw_view_check(name, residual, (B, ho, wo, C), "residual")
+    _dw_view_check(name, out, (B, ho, wo, C), "out")
+    if use_hip(x):
+        from . import hip_ops
+
+        return hip_ops.depthwise_conv2d(x, wp, bias, stride, pad, pad_mode, residual, out, (ho, wo))
+    y = _ref_depthwise_conv2d(x, wp, bias, stride, pad, pad_mode, residual)
+    if out is not None:
+        out.copy_(y)
+        y = out
+    return y
+
+
+def _ref_depthwise_conv_transpose2d(x, wp, bias, pad, pad_mode, crop):
+    dt = _cdt(x)
+    c = x.shape[-1]
+    w = wp.permute(2, 0, 1).unsqueeze(1).to(dt).contiguous()
+    y = F.conv_transpose2d(_dw_padded(x, pad, pad_mode), w, bias.to(dt) if bias is not None else None, stride=2,
+                           padding=crop, groups=c)
+    return y.permute(0, 2, 3, 1).to(x.dtype).contiguous()
+
+
+def depthwise_conv_transpose2d(x, wp, bias=None, in_padding=0, pad_mode="zeros", crop=0, out=None):
+    """Stride-2 depthwise transposed conv on NHWC:
+    ``conv_transpose2d(pad(x, in_padding, pad_mode), w, stride=2, padding=crop,
+    groups=C)``; output side ``(H + pt + pb - 1) * 2 - 2 * crop + kh``.  The HIP
+    kernel gathers (each output pixel sums the taps of its parity) and never
+    builds the padded tensor."""
+    name = "depthwise_conv_transpose2d"
+    pad = _dw_check(name, x, wp, bias, in_padding, pad_mode)
+    if not isinstance(crop, int) or crop < 0:
+        raise ValueError(f"{name}: crop {crop!r} must be a non-negative int")
+    B, H, W, C = x.shape
+    pt, pl, pb, pr = pad
+    ho = (H + pt + pb - 1) * 2 - 2 * crop + wp.shape[0]
+    wo = (W + pl + pr - 1) * 2 - 2 * crop + wp.shape[1]
+    if ho < 1 or wo < 1:
+        raise ValueError(f"{name}: crop {crop} leaves no output")
+    _dw_view_check(name, out, (B, ho, wo, C), "out")
+    if use_hip(x):
+        from . import hip_ops
+
+        return hip_ops.depthwise_conv_transpose2d(x, wp, bias, pad, pad_mode, crop, out, (ho, wo))
+    y = _ref_depthwise_conv_transpose2d(x, wp, bias, pad, pad_mode, crop)
+    if out is not None:
+        out.copy_(y)
+        y = out
+    return y
+
+
+# ----------------------------------------------------------------------------
 # 1-D convolutions on token-layout tensors [B, T, C] (HiFi-GAN / EnCodec)
 # ----------------------------------------------------------------------------
 def conv1d(x, wp, bias=None, padding=0, dilation=1, act=None, residual=None, out_scale=1.0, out=None):

@@ -591,6 +591,91 @@ def code_ok(act):
     return ACT[act] in (0, 2, 5, 6, 8, 9)
 
 
+# Depthwise NHWC conv and its stride-2 transpose (csrc/kernels/dwconv.hip)
+sig("csk_dwconv_tile", c_int)
+sig("csk_dwconv", c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p)
+sig("csk_dwconv_t", c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p)
+# dwconv.hip DW_TH / DW_TW / 8 * DW_CV: the output tile and channel block of one workgroup
+DWCONV_TH, DWCONV_TW, DWCONV_CB = 8, 16, 64
+DWCONV_VARIANTS = ("direct", "halo")
+DWCONV_STATS = [0]  # kernel launches (tests assert the kernel ran)
+
+
+def _dw_variant(kh, kw, stride):
+    """Forward variant, as measured (tools/dwconvbench.py, profiles/dwconv_r8.txt):
+    the LDS halo leads the 7x7 stride-1 conv by 0.5-1 us at every ConvNeXt
+    shape; the 4x4 stride-2 binomial is faster straight from L2 (6.4 vs 9.8 us
+    at 128^2 x 384), so stride 2 runs direct."""
+    return "halo" if stride == 1 and kh * kw > 1 else "direct"
+
+
+def _dw_operand(name, what, t, C):
+    """Pixel stride of an NHWC operand (bf16, channel slices allowed)."""
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: {what} must be bfloat16 on the HIP path, got {t.dtype}")
+    ps = _pix_stride(t)
+    if ps is None or ps % 8 or ps < C or t.data_ptr() % 16:
+        raise ValueError(f"{name}: {what} must be an NHWC tensor or channel slice (last dim contiguous, pixel "
+                         f"stride and channel offset multiples of 8), got strides {t.stride()}")
+    return ps
+
+
+def _dw_common(name, x, wp, bias, out, ho, wo):
+    B, H, W, C = x.shape
+    xs = _dw_operand(name, "x", x, C)
+    if not wp.is_cuda or wp.device != x.device or not wp.is_contiguous():
+        raise ValueError(f"{name}: wp must be a contiguous tensor on {x.device}")
+    if B > 65535:
+        raise ValueError(f"{name}: batch {B} > 65535")
+    bias_f32 = 0
+    if bias is not None:
+        if bias.dtype not in (torch.bfloat16, torch.float32) or not bias.is_contiguous() or bias.device != x.device:
+            raise ValueError(f"{name}: bias must be contiguous bf16 or fp32 on {x.device}")
+        if bias.data_ptr() % 16:
+            raise ValueError(f"{name}: bias must be 16-byte aligned")
+        bias_f32 = int(bias.dtype == torch.float32)
+    if out is None:
+        out = torch.empty((B, ho, wo, C), dtype=torch.bfloat16, device=x.device)
+    os_ = _dw_operand(name, "out", out, C)
+    return xs, os_, bias_f32, out
+
+
+def depthwise_conv2d(x, wp, bias, stride, pad, pad_mode, residual, out, out_hw, variant=None):
+    """``ops.depthwise_conv2d`` on the HIP kernel (arguments already validated
+    there: ``pad`` is the 4-tuple, ``out_hw`` the output size).  ``variant``:
+    "halo" / "direct", default ``_dw_variant``."""
+    name = "depthwise_conv2d"
+    B, H, W, C = x.shape
+    ho, wo = out_hw
+    kh, kw = wp.shape[0], wp.shape[1]
+    xs, os_, bias_f32, out = _dw_common(name, x, wp, bias, out, ho, wo)
+    rs = 0
+    if residual is not None:
+        rs = _dw_operand(name, "residual", residual, C)
+    variant = variant or _dw_variant(kh, kw, stride)
+    if variant not in DWCONV_VARIANTS:
+        raise ValueError(f"{name}: variant {variant!r} not in {DWCONV_VARIANTS}")
+    _lib.call("csk_dwconv", _p(x), _p(wp), _p(bias), bias_f32, _p(residual), _p(out), B, H, W, C, xs, rs, os_, ho, wo,
+              kh, kw, int(stride), pad[0], pad[1], int(pad_mode == "reflect"), DWCONV_VARIANTS.index(variant), _s())
+    DWCONV_STATS[0] += 1
+    return out
+
+
+def depthwise_conv_transpose2d(x, wp, bias, pad, pad_mode, crop, out, out_hw):
+    """``ops.depthwise_conv_transpose2d`` on the HIP gather kernel."""
+    name = "depthwise_conv_transpose2d"
+    B, H, W, C = x.shape
+    ho, wo = out_hw
+    xs, os_, bias_f32, out = _dw_common(name, x, wp, bias, out, ho, wo)
+    pt, pl, pb, pr = pad
+    _lib.call("csk_dwconv_t", _p(x), _p(wp), _p(bias), bias_f32, _p(out), B, H, W, C, xs, os_, ho, wo, wp.shape[0],
+              wp.shape[1], pt, pl, H + pt + pb, W + pl + pr, int(crop), int(pad_mode == "reflect"), _s())
+    DWCONV_STATS[0] += 1
+    return out
+
+
 sig("csk_axpby_nhwc", c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_int,
     c_void_p)
 
