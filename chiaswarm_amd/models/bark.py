@@ -12,10 +12,12 @@ Stages (geometry and token conventions of the public Bark release):
   4. EnCodec decoder: codebook embeddings -> causal SEANet decoder (weight-norm
      folded at load, reflect padding, ELU, 2-layer LSTM) -> 24 kHz waveform.
 
-MI355X path: all GPT projections are the MFMA GEMM with fused bias/GELU/
-residual epilogues; prefill and KV-cached decode both run the flash-attention
-kernel on strided views of a preallocated per-layer KV cache (no concatenation
-per token); decoder convs are the implicit-GEMM conv kernel with ELU fused
+MI355X path: prefill projections are the MFMA GEMM with fused bias/GELU/
+residual epilogues and the flash-attention kernel on strided views of a
+preallocated per-layer KV cache (no concatenation per token); the KV-cached
+decode step streams its weights through the GEMV kernel (LayerNorm in its
+prologue) and runs the split-KV decode attention, which also appends the new
+key / value: five launches per layer; decoder convs are the implicit-GEMM conv kernel with ELU fused
 into the epilogue and transposed convs in polyphase form.  The LSTM runs in
 fp32 through torch (MIOpen RNN).
 """
@@ -111,15 +113,17 @@ class _Attn(nn.Module):
         self.att_proj = Linear(c.n_embd, 3 * c.n_embd, bias=c.bias)
         self.out_proj = Linear(c.n_embd, c.n_embd, bias=c.bias)
 
-    def decode(self, x, residual, cache, pos_t, len_t):
-        """One-token step with device-side position / length (graph-capturable)."""
+    def decode(self, x, norm, cache, pos_t, len_t):
+        """One-token step with device-side position / length (graph-capturable):
+        ``norm`` (the block's first LayerNorm) runs in the QKV GEMV's prologue, the
+        new key / value go into the cache inside the attention kernel."""
         b = x.shape[0]
-        qkv = self.att_proj(x).view(b, 1, 3, self.nh, self.dh)
+        qkv = ops.gemv(x, self.att_proj.weight, self.att_proj.bias, ln=(norm.weight, norm.bias, norm.eps))
+        qkv = qkv.view(b, 1, 3, self.nh, self.dh)
         kc, vc = cache
-        kc.index_copy_(1, pos_t, qkv[:, :, 1])
-        vc.index_copy_(1, pos_t, qkv[:, :, 2])
-        o = ops.attention(qkv[:, :, 0], kc, vc, 1.0 / math.sqrt(self.dh), kv_len=len_t)
-        return self.out_proj(o.reshape(b, 1, -1), residual=residual)
+        o = ops.decode_attention(qkv[:, :, 0], kc, vc, 1.0 / math.sqrt(self.dh), len_t,
+                                 k_new=qkv[:, :, 1], v_new=qkv[:, :, 2], pos=pos_t)
+        return ops.gemv(o.reshape(b, 1, -1), self.out_proj.weight, self.out_proj.bias, residual=x)
 
     def forward(self, x, residual, causal, cache=None, pos=0):
         b, s, _ = x.shape
@@ -154,8 +158,11 @@ class _Block(nn.Module):
         return self.mlp.out_proj(self.mlp.in_proj(self.layernorm_2(x), act="gelu"), residual=x)
 
     def decode(self, x, cache, pos_t, len_t):
-        x = self.attn.decode(self.layernorm_1(x), x, cache, pos_t, len_t)
-        return self.mlp.out_proj(self.mlp.in_proj(self.layernorm_2(x), act="gelu"), residual=x)
+        """Five launches on the HIP path: QKV, attention (+ append), out-projection, MLP in, MLP out."""
+        x = self.attn.decode(x, self.layernorm_1, cache, pos_t, len_t)
+        n2, fc, proj = self.layernorm_2, self.mlp.in_proj, self.mlp.out_proj
+        h = ops.gemv(x, fc.weight, fc.bias, act="gelu", ln=(n2.weight, n2.bias, n2.eps))
+        return ops.gemv(h, proj.weight, proj.bias, residual=x)
 
 
 class BarkCausalGPT(nn.Module):
@@ -190,7 +197,8 @@ class BarkCausalGPT(nn.Module):
         x = x.to(self.lm_head.weight.dtype)
         for i, layer in enumerate(self.layers):
             x = layer.decode(x, self.cache[i], pos_t, len_t)
-        return self.lm_head(self.layernorm_final(x[:, -1])).float()
+        nf = self.layernorm_final
+        return ops.gemv(x[:, -1], self.lm_head.weight, None, ln=(nf.weight, nf.bias, nf.eps)).float()
 
     @torch.no_grad()
     def decode_step(self, token: int, pos: int):

@@ -961,6 +961,75 @@ def attention(q, k, v, scale=None, causal=False, kv_len=None, *, bias=None, kv_l
 
 
 # ----------------------------------------------------------------------------
+# KV-cached decode: one token (or a few rows) per step
+# ----------------------------------------------------------------------------
+def gemv(x, w, bias=None, *, act=None, residual=None, ln=None, out=None):
+    """y[..., N] = act(LayerNorm?(x)[..., K] @ w[N, K]^T + bias) + residual for the
+    handful of rows of a decode step; ``ln = (gamma, beta, eps)`` normalises the
+    rows first.  Defined as ``gemm(layer_norm(x, *ln), w, bias, residual=, act=)``,
+    which is what runs on the CPU and in reference mode.  On the HIP path up to 8
+    rows go to the weight-streaming GEMV kernel (LayerNorm in its prologue);
+    more rows, K not a multiple of 8 or a GEGLU activation run layer_norm + gemm.
+    ``out``: optional [rows, N] view (contiguous last dim) to write into."""
+    lead = x.shape[:-1]
+    k = x.shape[-1]
+    x2 = x.reshape(-1, k)
+    if use_hip(x):
+        from . import hip_ops
+
+        y = hip_ops.gemv(x2, w, bias, act, residual, ln, out)
+    else:
+        if ln is not None:
+            x2 = _ref_layer_norm(x2, ln[0], ln[1], ln[2])
+        y = _ref_gemm(x2, w, bias, residual, act)
+        if out is not None:
+            out.copy_(y)
+            y = out
+    return y.view(*lead, y.shape[-1]) if out is None else y
+
+
+def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=None, pos=None):
+    """One query per (b, h) over the first ``kv_len`` keys of a [B, S, H, D] KV
+    cache; returns [B, 1, H, D].  ``kv_len``: int32 [1] tensor on q's device,
+    clamped to [0, S] (0 gives zeros); on the HIP path the kernel reads it, so
+    the call is hipGraph-capturable.  With ``k_new`` / ``v_new`` ([B, 1, H, D]
+    views, e.g. slices of the QKV projection) the new token's key and value are
+    first written into the caches at index kv_len - 1.
+
+    Definition (CPU / reference): that write, then ``_ref_attention`` over the
+    first kv_len keys.  HIP: the split-KV decode kernel with the append fused in
+    for D in {32, 64, 128}; other head dims run index_copy_ + ``attention(kv_len=)``
+    (``pos``: optional long [1] device tensor holding kv_len - 1 for that
+    index_copy_, so a caller that has it spares the fallback deriving it)."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.device != q.device:
+        raise TypeError("decode_attention: kv_len must be an int32 tensor on the device of q")
+    if q.dim() != 4 or q.shape[1] != 1:
+        raise ValueError(f"decode_attention: q must be [B, 1, H, D], got {tuple(q.shape)}")
+    B, _, H, D = q.shape
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[2:] != (H, D):
+        raise ValueError(f"decode_attention: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} do not match "
+                         f"q {tuple(q.shape)}")
+    if (k_new is None) != (v_new is None):
+        raise ValueError("decode_attention: k_new and v_new come together")
+    if k_new is not None and (k_new.shape != q.shape or v_new.shape != q.shape):
+        raise ValueError(f"decode_attention: k_new / v_new {tuple(k_new.shape)} / {tuple(v_new.shape)} must be "
+                         f"{tuple(q.shape)}")
+    if use_hip(q):
+        from . import hip_ops
+
+        return hip_ops.decode_attention(q, k_cache, v_cache, scale, kv_len, k_new, v_new, pos)
+    n = min(max(int(kv_len.reshape(-1)[0].item()), 0), k_cache.shape[1])
+    if k_new is not None and n > 0:
+        k_cache[:, n - 1] = k_new[:, 0].to(k_cache.dtype)
+        v_cache[:, n - 1] = v_new[:, 0].to(v_cache.dtype)
+    if n == 0:
+        return torch.zeros_like(q)
+    return _ref_attention(q, k_cache[:, :n], v_cache[:, :n], scale, False)
+
+
+# ----------------------------------------------------------------------------
 # Image preprocessing
 # ----------------------------------------------------------------------------
 def canny(gray: torch.Tensor, low: float = 100.0, high: float = 200.0) -> torch.Tensor:

@@ -1258,3 +1258,161 @@ def xin_qkv(x, stat, gamma, beta, w, bi, colsum, bq, eps):
               _p(None if beta is None else beta.contiguous()), stat.shape[1], _p(w.contiguous()), _p(bi), _p(colsum),
               _p(bq), M, M // B, float(eps), _s())
     return h, qkv
+
+
+# ---------------------------------------------------------------------------
+# KV-cached decode: skinny-M GEMV (csrc/kernels/gemv.hip) and single-query
+# split-KV attention with the K/V append fused in (csrc/kernels/attn_decode.hip).
+# Called only where decode code asks for them (ops.gemv / ops.decode_attention):
+# ops.gemm / ops.attention dispatch as before.  CSK_DECODE=0 / set_decode(False):
+# both ops take their fallback (layer_norm + gemm; index_copy_ x2 + attention).
+# ---------------------------------------------------------------------------
+sig("csk_gemv", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_float, c_void_p)
+sig("csk_set_gemv_nt", c_int)
+sig("csk_attention_decode", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+    c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p)
+sig("csk_attn_decode_split")
+DECODE = os.environ.get("CSK_DECODE", "1") == "1"
+DECODE_STATS = {"gemv": 0, "decode_attention": 0}  # kernel launches per op (tests assert the kernels ran)
+GEMV_MAX_M = 8             # gemv.hip GV_MAX_M
+GEMV_LDS_FLOATS = 32768    # gemv.hip GV_LDS_FLOATS: padded rows x K fp32 the kernel keeps in LDS
+DECODE_SPLIT = 64          # attn_decode.hip AD_SPLIT: keys per workgroup
+DECODE_HEAD_DIMS = (32, 64, 128)
+_DECODE_WS: dict = {}      # (device, B, H, S, D) -> (fp32 partials, uint32 counters)
+
+
+def set_decode(on: bool):
+    """Decode kernels on / off (off: ``gemv`` and ``decode_attention`` take their
+    fallbacks).  Read at launch: a hipGraph captured before the call keeps the
+    kernels it was captured with (Bark: drop ``model._graph``)."""
+    global DECODE
+    DECODE = bool(on)
+
+
+def set_gemv_nt(on: bool):
+    """Non-temporal (default) or default-policy weight loads of the GEMV: the
+    A/B knob of tools/decodebench.py."""
+    _lib.call("csk_set_gemv_nt", int(bool(on)))
+
+
+def _aligned_rows(t, single_row_ok=False):
+    """t [R, C]: last dim contiguous, 16-byte aligned base and rows"""
+    return (t.stride(1) == 1 and t.data_ptr() % 16 == 0
+            and (t.stride(0) % 8 == 0 or (single_row_ok and t.shape[0] == 1)))
+
+
+def gemv(x2, w, bias=None, act=None, residual=None, ln=None, out=None):
+    """y[M, N] = act(LN?(x2)[M, K] @ w[N, K]^T + bias) + residual on the GEMV
+    kernel for M <= 8; ``ln = (gamma, beta, eps)``.  ``x2``, ``residual`` and
+    ``out`` may be row-strided views, ``w`` a view whose row stride is a
+    multiple of 8.  What the kernel does not take (M > 8, K % 8, GEGLU, rows
+    beyond its LDS budget) runs layer_norm + gemm instead."""
+    _bf16(x2, "gemv.x")
+    _bf16(w, "gemv.w")
+    M, K = x2.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"gemv: K mismatch {tuple(x2.shape)} x {tuple(w.shape)}")
+    code = ACT[act]
+    mt = 1 if M <= 1 else 2 if M <= 2 else 4 if M <= 4 else 8
+    if not DECODE or M < 1 or M > GEMV_MAX_M or K % 8 or K < 8 or code == 3 or mt * K > GEMV_LDS_FLOATS:
+        if ln is not None:
+            x2 = layer_norm(x2, ln[0], ln[1], ln[2])
+        y = gemm(x2, w, bias, residual, act, out=out if out is not None and out.is_contiguous() else None)
+        if out is not None and y is not out:
+            out.copy_(y)
+            return out
+        return y
+    if not _aligned_rows(x2, single_row_ok=True):
+        x2 = x2.contiguous()
+    if not _aligned_rows(w):
+        w = w.contiguous()
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
+    elif out.shape != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1 or out.device != x2.device:
+        raise ValueError(f"gemv: out must be a bf16 [{M}, {N}] view with a contiguous last dim")
+    ldr = 0
+    if residual is not None:
+        _bf16(residual, "gemv.residual")
+        residual = residual.reshape(M, N)
+        if residual.stride(1) != 1:
+            residual = residual.contiguous()
+        ldr = residual.stride(0)
+    if bias is not None:
+        _bf16(bias, "gemv.bias")
+        bias = bias.contiguous()
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:
+        gamma, beta, eps = ln
+        _bf16(gamma, "gemv.gamma")
+        if gamma.numel() != K or (beta is not None and beta.numel() != K):
+            raise ValueError(f"gemv: LayerNorm affine of {gamma.numel()} elements for K = {K}")
+        gamma = gamma.contiguous()
+        if gamma.data_ptr() % 16:
+            gamma = gamma.clone()
+        if beta is not None:
+            _bf16(beta, "gemv.beta")
+            beta = beta.contiguous()
+            if beta.data_ptr() % 16:
+                beta = beta.clone()
+    _lib.call("csk_gemv", _p(out), _p(x2), _p(w), _p(bias), _p(residual), _p(gamma), _p(beta), M, N, K,
+              x2.stride(0), w.stride(0), ldr, out.stride(0), code, float(eps), _s())
+    DECODE_STATS["gemv"] += 1
+    return out
+
+
+def _decode_ws(device, B, H, S, D):
+    """Partials and arrival counters of the split-KV decode attention, allocated
+    once per (device, shape) and zeroed at allocation (the kernel leaves the
+    counters at zero).  Launches that share them must be stream-ordered."""
+    key = (device, B, H, S, D)
+    ws = _DECODE_WS.get(key)
+    if ws is None:
+        nsplit = -(-S // DECODE_SPLIT)
+        ws = (torch.zeros(B * H * nsplit * (D + 2), dtype=torch.float32, device=device),
+              torch.zeros(B * H, dtype=torch.int32, device=device))
+        _DECODE_WS[key] = ws
+    return ws
+
+
+def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None):
+    """``ops.decode_attention`` on the HIP path (arguments validated there).
+    ``pos``: the caller's long [1] device tensor holding kv_len - 1, used by the
+    fallback's index_copy_ instead of deriving it from ``kv_len``."""
+    for t, n in ((q, "q"), (kc, "k_cache"), (vc, "v_cache"), (k_new, "k_new"), (v_new, "v_new")):
+        if t is not None:
+            _bf16(t, "decode_attention." + n)
+            if t.stride(-1) != 1:
+                raise ValueError("decode_attention: last dim must be contiguous")
+    B, _, H, D = q.shape
+    S = kc.shape[1]
+
+    def vec_ok(t):
+        return t is None or (t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:3]))
+
+    if not DECODE or D not in DECODE_HEAD_DIMS or B * H > 65535 or not (vec_ok(kc) and vec_ok(vc)):
+        if k_new is not None:
+            if pos is None:
+                pos = (kv_len.to(torch.long) - 1).clamp_(0, S - 1)
+            kc.index_copy_(1, pos, k_new)
+            vc.index_copy_(1, pos, v_new)
+        return attention(q, kc, vc, scale, kv_len=kv_len)
+    if not vec_ok(q):
+        q = q.contiguous()
+    if not vec_ok(k_new):
+        k_new = k_new.contiguous()
+    if not vec_ok(v_new):
+        v_new = v_new.contiguous()
+    o = torch.empty((B, 1, H, D), dtype=torch.bfloat16, device=q.device)
+    ws, cnt = _decode_ws(q.device, B, H, S, D)
+
+    def bh(t):
+        return (t.stride(0), t.stride(2)) if t is not None else (0, 0)
+
+    st = (c_int64 * 14)(*bh(q), *kc.stride()[:3], *vc.stride()[:3], *bh(k_new), *bh(v_new), *bh(o))
+    _lib.call("csk_attention_decode", _p(o), _p(q), _p(kc), _p(vc), _p(k_new), _p(v_new), st, B, H, S, D,
+              float(scale), _p(kv_len), _p(ws), _p(cnt), _s())
+    DECODE_STATS["decode_attention"] += 1
+    return o
