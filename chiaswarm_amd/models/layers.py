@@ -454,7 +454,16 @@ class Transformer2D(nn.Module):
         return self.proj_out(h.view(b, hh, ww, c), residual=x, gn_stats=True)
 
 
-class ResnetBlock2D(nn.Module):
+class ResnetBlock2D(Prepared):
+    """GroupNorm -> conv1 (+ time embedding) -> GroupNorm -> conv2 (+ shortcut).
+
+    A 1x1 ``conv_shortcut`` (``cin != cout``) is no kernel of its own where
+    ``ops.SC_FUSE`` is on and every channel count is a multiple of 64: its input
+    (both halves of a skip concat in ``forward_cat``) rides along as extra K
+    segments of conv2 (``ops.conv2d(extra=...)``), one fp32 accumulation, from
+    ONE packed [Cout, 9 Cout + Cin] weight and the folded bias built by
+    ``prepare()``.  The parameters (state-dict keys) are unchanged."""
+
     def __init__(self, cin, cout, temb_channels=None, groups=32, eps=1e-5, groups_out=None):
         super().__init__()
         self.norm1 = GroupNorm(groups, cin, eps=eps)
@@ -465,20 +474,93 @@ class ResnetBlock2D(nn.Module):
         self.conv_shortcut = Conv2d(cin, cout, 1, padding=0) if cin != cout else None
         self.out_channels = cout
 
-    def _conv2(self, h, sc, next_norm):
+    def prepare(self):
+        """Drop the fused shortcut pack; it is rebuilt from the current weights
+        on first use (``_sc_pack``: also after a device / dtype change or an
+        in-place weight update, e.g. a LoRA merge)."""
+        self.__dict__["_scf"] = None
+
+    def _sc_static(self) -> bool:
+        sc, c2 = self.conv_shortcut, self.conv2
+        return (sc is not None and sc.kernel_size == (1, 1) and sc.stride == (1, 1) and sc.padding == (0, 0)
+                and c2.kernel_size == (3, 3) and c2.stride == (1, 1) and c2.padding == (1, 1)
+                and c2.dilation == (1, 1) and sc.in_channels % 64 == 0 and c2.in_channels % 64 == 0
+                and c2.out_channels % 64 == 0 and self.norm1.weight.dim() == 1 and self.norm2.weight.dim() == 1)
+
+    def _sc_pack(self):
+        """(conv2 weight view [Cout, 3, 3, C], shortcut weight view [Cout, Cin],
+        folded bias) of one [Cout, 9 C + Cin] matrix.  While the pack is in use
+        conv2's own packed copy is released (``Conv2d._wp`` rebuilds it on demand)."""
+        sc, c2 = self.conv_shortcut, self.conv2
+        w2, ws, b2, bs = c2.weight, sc.weight, c2.bias, sc.bias
+        key = (w2.data_ptr(), w2._version, ws.data_ptr(), ws._version, None if b2 is None else b2._version,
+               None if bs is None else bs._version, w2.device, w2.dtype)
+        hit = self.__dict__.get("_scf")
+        if hit is None or hit[0] != key:
+            _, wv, (wsc,) = ops.pack_conv_extra(ops.pack_conv_weight(w2.detach()),
+                                                [ws.detach().reshape(sc.out_channels, sc.in_channels)])
+            bias = None
+            if b2 is not None or bs is not None:  # fp32 sum, rounded once
+                bias = sum(b.detach().float() for b in (b2, bs) if b is not None).to(w2.dtype)
+            hit = (key, (wv, wsc, bias))
+            self.__dict__["_scf"] = hit
+        if c2.__dict__.get("wp") is not None:
+            c2.wp = None
+        return hit[1]
+
+    def _sc_fuse(self, srcs):
+        """The shortcut of ``srcs`` (channel concat) as conv2's extra K segments:
+        (weight view, ((src, weight view), ...), bias), or None (unfused)."""
+        if not ops.SC_FUSE or not self._sc_static():
+            return None
+        cs = [int(t.shape[-1]) for t in srcs]
+        if sum(cs) != self.conv_shortcut.in_channels or any(c % 64 for c in cs) or any(t.dim() != 4 for t in srcs):
+            return None
+        wv, wsc, bias = self._sc_pack()
+        extra, off = [], 0
+        for t, c in zip(srcs, cs):
+            extra.append((t, wsc[:, off:off + c]))
+            off += c
+        return wv, tuple(extra), bias
+
+    def _shortcut(self, srcs):
+        """The unfused 1x1 shortcut of the channel concat ``srcs``."""
+        sc_conv = self.conv_shortcut
+        if len(srcs) == 1:
+            return sc_conv(srcs[0])
+        a, b = srcs
+        w = sc_conv.weight.view(sc_conv.out_channels, sc_conv.in_channels)
+        ca = a.shape[-1]
+        return ops.gemm(b, w[:, ca:], sc_conv.bias, residual=ops.gemm(a, w[:, :ca]))
+
+    def _conv2(self, h, sc, next_norm, fuse=None):
         """conv2 + shortcut; ``next_norm``: the GroupNorm the caller knows to
         consume the block output next (a transformer's input norm).  A split-K
         conv2 then applies it in its reduce kernel beside the raw output and the
-        result rides on the output (``GroupNorm.attach``)."""
+        result rides on the output (``GroupNorm.attach``).  ``fuse``
+        (``_sc_fuse``): the shortcut runs inside conv2, ``sc`` is its sources."""
+        conv2 = lambda residual, **kw: self.conv2(h, residual=residual, **kw)  # noqa: E731
+        if fuse is not None:
+            wv, extra, bias = fuse
+            if ops.conv_extra_fusable(h, wv, extra):
+                conv2 = lambda residual, **kw: ops.conv2d(h, wv, bias, 1, 1, extra=extra, **kw)  # noqa: E731
+                sc = None
+            else:
+                sc = self._shortcut(sc)
         if next_norm is None or next_norm.weight.dim() != 1:
-            return self.conv2(h, residual=sc, gn_stats=True)  # block output usually feeds the next GroupNorm
-        yn, out = self.conv2(h, residual=sc, norm=next_norm.after_conv(keep_raw=True), norm_optional=True)
+            return conv2(sc, gn_stats=True)  # block output usually feeds the next GroupNorm
+        yn, out = conv2(sc, norm=next_norm.after_conv(keep_raw=True), norm_optional=True)
         return next_norm.attach(out, yn)
 
     def forward(self, x, temb_proj=None, next_norm=None):
         """``temb_proj``: this block's [B, Cout] time projection (already
-        computed by the model's batched time-embedding GEMM).  A 1x1 shortcut
-        runs on a side stream, overlapping norm1 / conv1 / norm2."""
+        computed by the model's batched time-embedding GEMM).  An unfused 1x1
+        shortcut runs on a side stream, overlapping norm1 / conv1 / norm2."""
+        fuse = self._sc_fuse((x,))
+        if fuse is not None:
+            h = self.norm1(x, silu=True)
+            h = self.conv1(h, bias2d=temb_proj, norm=self.norm2.after_conv(silu=True))
+            return self._conv2(h, (x,), next_norm, fuse)
         sc = x
         with ops.side_branch(x) as br:
             if self.conv_shortcut is not None:
@@ -493,9 +575,9 @@ class ResnetBlock2D(nn.Module):
     def forward_cat(self, a, b, temb_proj=None, next_norm=None):
         """forward() of the channel concat [a | b] (a UNet skip connection)
         without materialising the concat on the HIP path: norm1 reads both
-        tensors in place and the 1x1 shortcut runs as two accumulating GEMMs
-        (the concat cost a full read + write of both tensors per up-block
-        ResNet)."""
+        tensors in place and the 1x1 shortcut reads them as two K segments of
+        conv2 (unfused: two accumulating GEMMs; the concat cost a full read +
+        write of both tensors per up-block ResNet)."""
         sc_conv = self.conv_shortcut
         hn = None
         if ops.use_hip(a) and sc_conv is not None and sc_conv.kernel_size == (1, 1) and self.norm1.weight.dim() == 1:
@@ -503,6 +585,10 @@ class ResnetBlock2D(nn.Module):
                                     self.norm1.eps, silu=True)
         if hn is None:
             return self.forward(ops.cat_channels(a, b), temb_proj, next_norm)
+        fuse = self._sc_fuse((a, b))
+        if fuse is not None:
+            h = self.conv1(hn, bias2d=temb_proj, norm=self.norm2.after_conv(silu=True))
+            return self._conv2(h, (a, b), next_norm, fuse)
         w = sc_conv.weight.view(sc_conv.out_channels, sc_conv.in_channels)
         ca = a.shape[-1]
         with ops.side_branch(a) as br:  # shortcut GEMMs overlap conv1 / norm2

@@ -505,7 +505,7 @@ def conv_out_size(h, w, kh, kw, stride, padding, up2x=False, dilation=1):
 
 
 def _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_scale=1.0, dilation=1,
-                residual2=None, res_scale=1.0):
+                residual2=None, res_scale=1.0, extra=None):
     dt = _cdt(x)
     # NHWC tensor viewed as channels-last NCHW: no copies, MIOpen NHWC kernels
     xn = x.to(dt).permute(0, 3, 1, 2)
@@ -519,6 +519,8 @@ def _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, 
     else:
         y = F.conv2d(F.pad(xn, (pl, pr, pt, pb)), w, b, stride=stride, dilation=dilation)
     y = y.permute(0, 2, 3, 1)
+    for a, wa in extra or ():
+        y = y + a.to(dt) @ wa.to(dt).t()
     if bias2d is not None:
         y = y + bias2d.to(dt)[:, None, None, :]
     y = apply_act(y, act)
@@ -531,9 +533,42 @@ def _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, 
     return y.to(x.dtype).contiguous()
 
 
+# A ResNet's 1x1 shortcut folded into its conv2 as extra K segments
+# (conv2d(extra=...)); CSK_SC_FUSE=0: the shortcut stays its own GEMM(s) and
+# conv2 adds it as a residual
+SC_FUSE = os.environ.get("CSK_SC_FUSE", "1") == "1"
+
+
+def pack_conv_extra(wp: torch.Tensor, ws) -> tuple:
+    """One [Cout, kh*kw*Cin + sum Ci] K-contiguous matrix from a packed conv
+    weight [Cout, kh, kw, Cin] and the [Cout, Ci] weights of its extra K
+    segments.  Returns (matrix, conv view [Cout, kh, kw, Cin], segment views):
+    the views are what ``conv2d(..., extra=...)`` takes."""
+    cout, kh, kw, cin = wp.shape
+    wf = torch.cat([wp.reshape(cout, -1)] + [w.reshape(cout, -1).to(wp.dtype) for w in ws], dim=1).contiguous()
+    k0, views = kh * kw * cin, []
+    off = k0
+    for w in ws:
+        c = w.reshape(cout, -1).shape[1]
+        views.append(wf[:, off:off + c])
+        off += c
+    return wf, wf[:, :k0].unflatten(1, (kh, kw, cin)), tuple(views)
+
+
+def conv_extra_fusable(x, wp, extra, stride=1, padding=1, up2x=False, dilation=1) -> bool:
+    """``conv2d(..., extra=extra)`` is available for this call: always on the
+    plain-PyTorch path, on the HIP path under the kernels' conditions
+    (``hip_ops.conv_extra_ok``)."""
+    if not use_hip(x):
+        return True
+    from . import hip_ops
+
+    return hip_ops.conv_extra_ok(x, wp, extra, stride, padding, up2x, dilation)
+
+
 def conv2d(x, wp, bias=None, stride=1, padding=1, residual=None, up2x=False, bias2d=None, act=None,
            out_scale=1.0, out=None, dilation=1, gn_stats=False, residual2=None, res_scale=1.0, out_u8=False,
-           norm=None, norm_optional=False):
+           norm=None, norm_optional=False, extra=None):
     """NHWC conv.  ``wp``: packed [Cout, kh, kw, Cin].  ``up2x`` fuses a
     nearest-neighbour x2 upsample into the input addressing; ``bias2d`` [B, Cout]
     is a per-sample channel bias (ResNet time-embedding add) fused in the
@@ -551,19 +586,24 @@ def conv2d(x, wp, bias=None, stride=1, padding=1, residual=None, up2x=False, bia
     ``keep_raw`` (``out=``, the raw output's buffer, needs it).  A split-K plan on the HIP path applies it in the reduce
     kernel, so the raw tensor is never written unless kept.  ``norm_optional``
     (with ``keep_raw``): apply the norm only where it costs no extra kernel,
-    else return (None, raw) and leave it to the consumer of the raw tensor."""
+    else return (None, raw) and leave it to the consumer of the raw tensor.
+    ``extra = ((a, wa), (b, wb))`` (one or two pairs): extra K segments,
+    y = act(conv(x) + a . wa^T + b . wb^T + bias + bias2d) * out_scale + residual
+    with ``a`` / ``b`` NHWC [B, Ho, Wo, Ci] and ``wa`` / ``wb`` [Cout, Ci]; the
+    HIP path runs them inside the conv's K loop and needs ``wp`` and the
+    segment weights to come from ``pack_conv_extra`` (``conv_extra_fusable``)."""
     if use_hip(x):
         from . import hip_ops
 
         return hip_ops.conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, out, dilation,
                               gn_stats, residual2=residual2, res_scale=res_scale, out_u8=out_u8, norm=norm,
-                              norm_optional=norm_optional)
+                              norm_optional=norm_optional, extra=extra)
     if norm is not None and (out_u8 or residual2 is not None or res_scale != 1.0):
         raise ValueError("conv2d: norm with out_u8 / residual2 / res_scale")
     if norm is not None and out is not None and not norm[5]:
         raise ValueError("conv2d: out= with norm is the raw output: it needs keep_raw")
     y = _ref_conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act, out_scale, dilation,
-                    residual2, res_scale)
+                    residual2, res_scale, extra)
     if out_u8:
         y = (y.float().clamp(0, 1) * 255).round().to(torch.uint8)
     if out is not None:

@@ -358,6 +358,68 @@ sig("csk_splitk_gn_fused_ok", c_int, c_int, c_int, c_int)
 sig("csk_conv2d_gn", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_void_p)
+# conv with extra K segments (a ResNet's 1x1 shortcut folded into its conv2's K loop)
+sig("csk_conv2d_ex2", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+    c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p)
+sig("csk_conv2d_gn2", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
+    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+    c_int, c_void_p)
+SC_FUSE_STATS = [0]  # conv2d(extra=...) launches (tests assert the fused path ran)
+# tiles that walk extra K segments: the LDS-DMA rings (gemm_glds.hip, gemm8p.hip gemm8r_kernel)
+XS_TILES = tuning.GLDS | {33, 34}
+# (B, H, W, Cin, Cout, segment channels) the fused conv measured slower at than
+# conv2 + the shortcut GEMMs it replaces (tools/convbench.py --shortcut): kept unfused
+SC_FUSE_OFF = set()
+
+
+def conv_extra_ok(x, wp, extra, stride=1, padding=1, up2x=False, dilation=1) -> bool:
+    """``conv2d(extra=...)`` takes this call on the HIP path: FAST LDS-DMA
+    staging (every channel count a multiple of 64), 3x3-style same-size geometry
+    (stride 1, no upsample, dilation 1, output size == input size), sources that
+    are 16-byte aligned NHWC tensors / channel slices of the output's
+    [B, Ho, Wo] with a pixel stride that is a multiple of 8, and a weight pack
+    ``fused_weight`` recognises."""
+    from . import conv_out_size
+
+    if not extra or len(extra) > 2 or x.dim() != 4 or x.dtype != torch.bfloat16:
+        return False
+    B, H, W, Cin = x.shape
+    Cout, kh, kw, _ = wp.shape
+    if stride != 1 or up2x or dilation != 1 or Cin % 64 or conv_out_size(H, W, kh, kw, 1, padding) != (H, W):
+        return False
+    xs = _pix_stride(x)
+    if xs is None or xs % 8 or x.data_ptr() % 16:
+        return False
+    for a, wa in extra:
+        if a.dtype != torch.bfloat16 or a.dim() != 4 or tuple(a.shape[:3]) != (B, H, W) or a.shape[3] % 64:
+            return False
+        ps = _pix_stride(a)
+        if ps is None or ps % 8 or a.data_ptr() % 16 or tuple(wa.shape) != (Cout, a.shape[3]):
+            return False
+    if (B, H, W, Cin, Cout, tuple(a.shape[3] for a, _ in extra)) in SC_FUSE_OFF:
+        return False
+    return fused_weight(wp, extra) is not None
+
+
+def fused_weight(wp, extra):
+    """The [Cout, kh*kw*Cin + Ca (+ Cb)] K-contiguous matrix that ``wp`` and the
+    segment weights are consecutive column slices of (``ops.pack_conv_extra``),
+    or None when they are separate tensors."""
+    Cout, kh, kw, Cin = wp.shape
+    k0 = kh * kw * Cin
+    K = k0 + sum(w.shape[1] for _, w in extra)
+    if wp.dtype != torch.bfloat16 or wp.stride() != (K, kw * Cin, Cin, 1) or wp.data_ptr() % 16:
+        return None
+    off = k0
+    for _, w in extra:
+        if w.dtype != wp.dtype or w.stride() != (K, 1) or w.data_ptr() != wp.data_ptr() + 2 * off:
+            return None
+        off += w.shape[1]
+    return torch.as_strided(wp, (Cout, K), (K, 1))
+
+
 SKGN_FUSED = os.environ.get("CSK_SKGN_FUSED", "1") == "1"
 # conv2d(norm=...) calls: (norm applied in the reduce, conv + GroupNorm kernels here,
 # norm_optional: raw returned and the norm left to its consumer)
@@ -407,7 +469,7 @@ def _skgn_ok(split, K, M, Cout, rows_per_b, ys, code, gamma, beta, groups, silu,
 
 
 def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_scale=1.0, out=None, dilation=1,
-           gn_stats=False, residual2=None, res_scale=1.0, out_u8=False, norm=None, norm_optional=False):
+           gn_stats=False, residual2=None, res_scale=1.0, out_u8=False, norm=None, norm_optional=False, extra=None):
     """NHWC conv.  ``x``, ``residual`` and ``out`` may be channel-slice views of
     wider NHWC buffers (last dim contiguous): the kernel takes their pixel
     strides, so dense/concat blocks need no copies.  ``residual2`` /
@@ -420,9 +482,19 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
     with ``keep_raw``.  A split-K plan applies it in its reduce kernel
     (SKGN_STATS[0]); anything else is this conv followed by ``group_norm``, or,
     with ``norm_optional`` (and ``keep_raw``), returns (None, raw) and leaves the
-    norm to the consumer of the raw tensor (its epilogue statistics attached)."""
+    norm to the consumer of the raw tensor (its epilogue statistics attached).
+    ``extra = ((a, wa), (b, wb))``: y = conv(x) + a . wa^T (+ b . wb^T) as extra
+    K segments of the conv's own K loop (one fp32 accumulation); ``wp`` and the
+    segment weights are slices of one ``ops.pack_conv_extra`` matrix and
+    ``conv_extra_ok`` holds, anything else is an error."""
     from . import conv_out_size, norm_padding
 
+    if extra is not None:
+        if out_u8 or residual2 is not None or res_scale != 1.0:
+            raise ValueError("conv2d: extra with out_u8 / residual2 / res_scale")
+        if not conv_extra_ok(x, wp, extra, stride, padding, up2x, dilation):
+            raise ValueError("conv2d: extra K segments need conv_extra_ok() (64-channel multiples, same-size "
+                             "stride-1 conv, aligned NHWC sources, one packed weight)")
     if norm is not None:
         if out_u8 or residual2 is not None or res_scale != 1.0:
             raise ValueError("conv2d: norm with out_u8 / residual2 / res_scale")
@@ -445,7 +517,12 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
         x = pad_last(x, cp)
         wp = pad_last(wp.contiguous(), cp)
         Cin = xs = cp
-    wp = wp.contiguous()
+    wf, xseg = None, ()
+    if extra is not None:
+        wf = fused_weight(wp, extra)
+        xseg = tuple((a, _pix_stride(a), a.shape[3]) for a, _ in extra)
+    else:
+        wp = wp.contiguous()
     pt, pl, pb, pr = norm_padding(padding)
     Ho, Wo = conv_out_size(H, W, kh, kw, stride, padding, up2x, dilation)
     if out_u8:
@@ -476,14 +553,24 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
         if bias2d.stride(1) != 1 or bias2d.data_ptr() % 16 or bias2d.stride(0) % 8:
             bias2d = bias2d.contiguous()
         b2s = bias2d.stride(0) if B > 1 else Cout
-    M, K = B * Ho * Wo, kh * kw * Cin
+    M, K = B * Ho * Wo, kh * kw * Cin + sum(s[2] for s in xseg)
     code = ACT[act]
+    # the segment arguments of the *2 entry points: (a, pixel stride, channels) x 2
+    sargs = ()
+    if xseg:
+        sb = xseg[1] if len(xseg) > 1 else (None, 0, 0)
+        sargs = (_p(xseg[0][0]), xseg[0][1], xseg[0][2], _p(sb[0]), sb[1], sb[2])
 
     def run(tile, split, part=None):
         nonlocal out
         if out is None:  # norm without keep_raw, and the reduce does not apply it (or tuning.choose is timing plans)
             out = torch.empty(oshape, dtype=torch.bfloat16, device=x.device)
         ws = _ws(split, M, Cout, x.device)
+        if xseg:
+            _lib.call("csk_conv2d_ex2", _p(out), _p(x), _p(wf), _p(bias), _p(bias2d), b2s, _p(residual),
+                      B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, 0, xs, ys, rs, code,
+                      float(out_scale), int(dilation), _p(part), tile, split, _p(ws), *sargs, _s())
+            return
         _lib.call("csk_conv2d_ex", _p(out), _p(x), _p(wp), _p(bias), _p(bias2d), b2s, _p(residual),
                   B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, int(bool(up2x)), xs, ys, rs, code,
                   float(out_scale), int(dilation), _p(part), tile, split, _p(ws), _s())
@@ -500,7 +587,12 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
     if kh != kw or dilation != 1:
         key += f":{kw}:{dilation}"
     narrow = Cout < 16
-    if (CONV_TILE and kh == 3 and kw == 3 and stride == 1 and (pt, pl, pb, pr) == (1, 1, 1, 1) and dilation == 1
+    if xseg:
+        # its own entries (K differs); a miss runs the unfused conv's plan
+        fkey = key + ":x" + ":".join(str(s[2]) for s in xseg)
+        tile, split = tuning.choose_extra(fkey, key, M, Cout, K, run, XS_TILES)
+        SC_FUSE_STATS[0] += 1
+    elif (CONV_TILE and kh == 3 and kw == 3 and stride == 1 and (pt, pl, pb, pr) == (1, 1, 1, 1) and dilation == 1
             and bias2d is None and not gn_stats
             and code in (0, 2, 5, 6, 8, 9)
             and (Cout == 32 or (Cout == 64 and CONV_TILE64) or (Cout <= 16 and M >= CONV_TILE_NARROW_MIN_PX))
@@ -513,7 +605,7 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
                   Cout, xs, ys, rs, rs2, code, float(out_scale), float(res_scale), int(bool(up2x)), 0, _s())
         CONV_TILE_STATS[0] += 1
         return out  # never with a norm: it sets gn_stats, which this kernel does not produce
-    if residual2 is not None or res_scale != 1.0:
+    elif residual2 is not None or res_scale != 1.0:
         # the implicit GEMM's epilogue has one unscaled residual: conv into a
         # temporary, then one combining pass (residual2 is read before out is written)
         y = conv2d(x, wp, bias, stride, padding, None, up2x, bias2d, act, out_scale, None, dilation)
@@ -523,17 +615,19 @@ def conv2d(x, wp, bias, stride, padding, residual, up2x, bias2d, act=None, out_s
             y = y + residual2
         out.copy_(y)
         return out
-    tile, split = tuning.choose(key, M, Cout, K, run)
+    else:
+        tile, split = tuning.choose(key, M, Cout, K, run)
     if norm is not None:
         gamma, beta, groups, eps, silu, keep_raw = norm
         if ys == Cout and _skgn_ok(split, K, M, Cout, Ho * Wo, ys, code, gamma, beta, groups, silu, bias, bias2d, b2s,
                                    residual, rs, out, keep_raw):
             yn = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
             ws = _ws(split, M, Cout, x.device)
-            _lib.call("csk_conv2d_gn", _p(out) if keep_raw else None, _p(x), _p(wp), _p(bias), _p(bias2d), b2s,
+            _lib.call("csk_conv2d_gn2" if xseg else "csk_conv2d_gn", _p(out) if keep_raw else None, _p(x),
+                      _p(wf if xseg else wp), _p(bias), _p(bias2d), b2s,
                       _p(residual), B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, int(bool(up2x)), xs, ys, rs,
                       float(out_scale), int(dilation), tile, split, _p(ws), _p(yn), _p(gamma), _p(beta), int(groups),
-                      float(eps), int(bool(silu)), int(bool(keep_raw)), _s())
+                      float(eps), int(bool(silu)), int(bool(keep_raw)), *sargs, _s())
             SKGN_STATS[0] += 1
             if SKGN_SITES is not None:
                 SKGN_SITES.append((B, Ho, Wo, Cin, Cout, split, bool(keep_raw)))

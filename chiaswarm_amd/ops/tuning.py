@@ -152,19 +152,25 @@ def current_context() -> str | None:
     return getattr(_CTX, "name", None)
 
 
-def choose(key: str, M: int, N: int, K: int, runner) -> tuple[int, int]:
-    """runner(tile, ksplit) launches the kernel once (used only when tuning)."""
-    t = table()
+def _lookup(t, key):
     ctx = getattr(_CTX, "name", None)
     hit = t.get(f"{ctx}|{key}") if ctx else None
-    if hit is None:
-        hit = t.get(key)
+    return t.get(key) if hit is None else hit
+
+
+def choose(key: str, M: int, N: int, K: int, runner, tiles=None) -> tuple[int, int]:
+    """runner(tile, ksplit) launches the kernel once (used only when tuning).
+    ``tiles``: the only tiles to time (``choose_extra``)."""
+    t = table()
+    hit = _lookup(t, key)
     if hit is not None:
         return int(hit[0]), int(hit[1])
     if os.environ.get("CSK_AUTOTUNE") == "1" and not torch.cuda.is_current_stream_capturing():
         with _LOCK:
             best, best_ms = None, float("inf")
             for tile, split in candidates(M, N, K):
+                if tiles is not None and (tile not in tiles or split < 0):
+                    continue
                 try:
                     ms = _time(lambda: runner(tile, split))
                 except RuntimeError:
@@ -175,3 +181,18 @@ def choose(key: str, M: int, N: int, K: int, runner) -> tuple[int, int]:
                 t[key] = [best[0], best[1], round(best_ms * 1000, 2)]
                 return best
     return heuristic(M, N, K)
+
+
+def choose_extra(key: str, like: str, M: int, N: int, K: int, runner, tiles) -> tuple[int, int]:
+    """Plan of a conv with extra K segments (key = the conv's key + the segment
+    channels, its own entries because K differs).  Only ``tiles`` walk the
+    segments (the LDS-DMA rings), split through the reduce kernel.  A miss runs
+    the plan of ``like``, the same conv without the segments, where its tile is
+    one of them (an in-kernel fixup split as a plain one), else 128x128."""
+    if _lookup(table(), key) is not None or os.environ.get("CSK_AUTOTUNE") == "1":
+        tile, split = choose(key, M, N, K, runner, tiles)
+        if _lookup(table(), key) is not None:
+            return tile, split
+    hit = _lookup(table(), like)  # (never tuned here: the runner is the fused conv's)
+    tile, split = (int(hit[0]), int(hit[1])) if hit is not None else heuristic(M, N, K)
+    return (tile if tile in tiles else 11), abs(split)

@@ -903,16 +903,50 @@ CSK_API int csk_gemm(void* C, const void* A, const void* W, const void* bias, co
 // buffers (>= channel counts: lets dense blocks read and write channel slices of
 // one concat buffer without copies).
 // b2s: row stride of bias2d ([B][b2s], 0 -> Cout)
+// Extra K segments (csk_conv2d_ex2 / csk_conv2d_gn2): up to two NHWC sources of
+// the output's [B][Ho][Wo], c channels at pixel stride ld, appended to the K
+// dimension after the taps; Wp is then [Cout][kh * kw * Cin + sum c].
+struct ConvSegs {
+  const void* p[2];
+  int ld[2], c[2];
+  int n;
+};
+
 static int conv2d_impl(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
                        const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
                        int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, int act, float out_scale, int dil,
-                       void* gn_part, int tile, int ksplit, void* ws, hipStream_t stream, const GnFuseArgs* gn) {
+                       void* gn_part, int tile, int ksplit, void* ws, hipStream_t stream, const GnFuseArgs* gn,
+                       const ConvSegs* segs = nullptr) {
   if (Cin % 8 != 0 || xs % 8 != 0 || xs < Cin || (b2s != 0 && b2s < Cout)) return (int)hipErrorInvalidValue;
+  int kx = 0;  // K elements of the extra segments
+  if (segs && segs->n > 0) {
+    // the FAST staging of the LDS-DMA ring kernels only (gemm_glds.hip, gemm8p.hip
+    // gemm8r_kernel), split-K through the reduce kernel; anything else is an error
+    if (segs->n > 2 || !(glds_tile(tile) || tile == 33 || tile == 34) || ksplit < 0) return (int)hipErrorInvalidValue;
+    if (stride != 1 || up2x || (dil != 0 && dil != 1) || Ho != H || Wo != W || Cin % BK != 0 || (size_t)X % 16 != 0)
+      return (int)hipErrorInvalidValue;
+    for (int i = 0; i < segs->n; ++i) {
+      const int c = segs->c[i], ld = segs->ld[i];
+      if (!segs->p[i] || (size_t)segs->p[i] % 16 != 0 || c <= 0 || c % BK != 0 || ld % 8 != 0 || ld < c ||
+          (size_t)(c + BK) * sizeof(bf16_t) > (size_t)csk_zero_bytes())
+        return (int)hipErrorInvalidValue;
+      kx += c;
+    }
+  }
   GemmArgs a{};
   a.A = (const bf16_t*)X; a.W = (const bf16_t*)Wp; a.C = (bf16_t*)Y;
   a.bias = (const bf16_t*)bias; a.bias2d = (const bf16_t*)bias2d; a.res = (const bf16_t*)res;
-  a.M = B * Ho * Wo; a.N = Cout; a.K = kh * kw * Cin; a.lda = xs; a.ldb = kh * kw * Cin; a.ldc = ys;
+  a.M = B * Ho * Wo; a.N = Cout; a.K = kh * kw * Cin + kx; a.lda = xs; a.ldb = a.K; a.ldc = ys;
   a.ldr = rs > 0 ? rs : ys; a.rows_per_b = Ho * Wo;
+  if (kx) {
+    a.xs_n = segs->n;
+    for (int i = 0; i < segs->n; ++i) {
+      a.xs_ptr[i] = (const bf16_t*)segs->p[i];
+      a.xs_ld[i] = segs->ld[i];
+      a.xs_c[i] = segs->c[i];
+      a.xs_end[i] = a.xs_ptr[i] + ((size_t)B * Ho * Wo - 1) * segs->ld[i] + segs->c[i];
+    }
+  }
   a.act = act; a.out_scale = out_scale;
   a.H = H; a.Wd = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.kh = kh; a.kw = kw; a.stride = stride; a.pt = pt; a.pl = pl;
   a.up2x = up2x;
@@ -935,6 +969,20 @@ CSK_API int csk_conv2d_ex(void* Y, const void* X, const void* Wp, const void* bi
                      rs, act, out_scale, dil, gn_part, tile, ksplit, ws, stream, nullptr);
 }
 
+// csk_conv2d_ex with extra K segments: y = conv(X) + A . Wa^T (+ B . Wb^T) in ONE
+// fp32 accumulation (a ResNet's conv2 with its 1x1 shortcut folded in), Wp =
+// [Cout][kh * kw * Cin | ca | cb] K-contiguous.  xb null / cb 0: one segment.
+CSK_API int csk_conv2d_ex2(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
+                           const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
+                           int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, int act, float out_scale, int dil,
+                           void* gn_part, int tile, int ksplit, void* ws, const void* xa, int xa_ld, int ca,
+                           const void* xb, int xb_ld, int cb, hipStream_t stream) {
+  if (!xa) return (int)hipErrorInvalidValue;
+  const ConvSegs sg{{xa, xb}, {xa_ld, xb_ld}, {ca, cb}, xb ? 2 : 1};
+  return conv2d_impl(Y, X, Wp, bias, bias2d, b2s, res, B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho, Wo, up2x, xs, ys,
+                     rs, act, out_scale, dil, gn_part, tile, ksplit, ws, stream, nullptr, &sg);
+}
+
 // csk_conv2d_ex of a split-K plan (ksplit > 1, no activation) whose reduce also
 // applies the GroupNorm (+ SiLU) that consumes the output
 // (splitk_reduce_gn_apply_kernel): Yn [B][Ho][Wo][Cout] contiguous gets the
@@ -953,6 +1001,23 @@ CSK_API int csk_conv2d_gn(void* Y, const void* X, const void* Wp, const void* bi
   return conv2d_impl(keep_raw ? Y : Yn, X, Wp, bias, bias2d, b2s, res, B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho,
                      Wo, up2x, xs, keep_raw ? ys : Cout, rs, ACT_NONE, out_scale, dil, nullptr, tile, ksplit, ws, stream,
                      &gn);
+}
+
+// csk_conv2d_gn with extra K segments (csk_conv2d_ex2)
+CSK_API int csk_conv2d_gn2(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, int b2s,
+                           const void* res, int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pt,
+                           int pl, int Ho, int Wo, int up2x, int xs, int ys, int rs, float out_scale, int dil, int tile,
+                           int ksplit, void* ws, void* Yn, const void* gamma, const void* beta, int groups, float eps,
+                           int silu, int keep_raw, const void* xa, int xa_ld, int ca, const void* xb, int xb_ld, int cb,
+                           hipStream_t stream) {
+  if (ksplit <= 1 || !ws || !Yn || (keep_raw && !Y) || !xa) return (int)hipErrorInvalidValue;
+  GnFuseArgs gn{};
+  gn.y = (bf16_t*)Yn; gn.gamma = (const bf16_t*)gamma; gn.beta = (const bf16_t*)beta;
+  gn.groups = groups; gn.eps = eps; gn.silu = silu; gn.keep_raw = keep_raw;
+  const ConvSegs sg{{xa, xb}, {xa_ld, xb_ld}, {ca, cb}, xb ? 2 : 1};
+  return conv2d_impl(keep_raw ? Y : Yn, X, Wp, bias, bias2d, b2s, res, B, H, W, Cin, Cout, kh, kw, stride, pt, pl, Ho,
+                     Wo, up2x, xs, keep_raw ? ys : Cout, rs, ACT_NONE, out_scale, dil, nullptr, tile, ksplit, ws, stream,
+                     &gn, &sg);
 }
 
 CSK_API int csk_conv2d(void* Y, const void* X, const void* Wp, const void* bias, const void* bias2d, const void* res,

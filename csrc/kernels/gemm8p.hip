@@ -284,7 +284,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const GemmArgs args) {
 // scalar branch on the SGPR wave id).  FAST staging only (K % 64 == 0, conv
 // Cin % 64 == 0); no fused LN / row statistics / GEGLU (host falls back).
 // ---------------------------------------------------------------------------
-template <int BN, int S, bool CONV>
+// XS: the conv's K loop also walks GemmArgs' extra segments (gemm_common.h ConvWalk)
+template <int BN, int S, bool CONV, bool XS = false>
 __global__ __launch_bounds__(512, 1) void gemm8r_kernel(const GemmArgs args) {
   constexpr int BM = 256, WM = 4, WN = 2, NW = 8;
   constexpr int WTM = BM / WM, WTN = BN / WN;
@@ -346,21 +347,21 @@ __global__ __launch_bounds__(512, 1) void gemm8r_kernel(const GemmArgs args) {
     const int n = n0 + (i * NW + wid) * 8 + lrow;
     fb[i] = (n < N && (i < IBL || xb)) ? args.W + (size_t)n * args.ldb + kbeg + lchunk * 8 : zero;
   }
-  int f_ky = 0, f_kx = 0, f_c = 0;
+  ConvWalk fw{0, 0, 0, args.Cin, -1};
+  ConvSrc fs{args.A, args.a_end, args.lda, 0, 0, true};
   auto set_rows = [&]() {
+    fs = conv_walk_src<XS>(args, fw);
 #pragma unroll
     for (int i = 0; i < IA; ++i) {
-      const int ih = a_ihb[i] + f_ky * args.dil, iw = a_iwb[i] + f_kx * args.dil;
-      const bool v = ih >= 0 && ih < Hin && iw >= 0 && iw < Win;
+      // (a segment's centre "tap": an invalid row's ih stays negative, -30000 + pt)
+      const int ih = a_ihb[i] + fs.dy, iw = a_iwb[i] + fs.dx;
+      const bool v = fs.ok && ih >= 0 && ih < Hin && iw >= 0 && iw < Win;
       const int sh = args.up2x ? (ih >> 1) : ih, sw = args.up2x ? (iw >> 1) : iw;
-      fa[i] = v ? args.A + (a_bbase[i] + (size_t)sh * args.Wd + sw) * args.lda + lchunk * 8 : zero;
+      fa[i] = v ? fs.base + (a_bbase[i] + (size_t)sh * args.Wd + sw) * fs.ld + lchunk * 8 : zero;
     }
   };
   if constexpr (CONV) {
-    const int tap = kbeg / args.Cin;
-    f_c = kbeg - tap * args.Cin;
-    f_ky = tap / args.kw;
-    f_kx = tap - f_ky * args.kw;
+    fw = conv_walk_begin<XS>(args, kbeg);
     set_rows();
   }
 
@@ -369,8 +370,9 @@ __global__ __launch_bounds__(512, 1) void gemm8r_kernel(const GemmArgs args) {
     bf16_t* bs = as + BM * BK;
 #pragma unroll
     for (int i = 0; i < IA; ++i) {
-      const bf16_t* src = CONV ? fa[i] + f_c : fa[i];
-      dma16<SITE_8R_A>(args, src, as + (i * NW + wid) * 8 * BK, smem, SMEM_MAIN);
+      const bf16_t* src = CONV ? fa[i] + fw.c : fa[i];
+      if constexpr (XS) dma16<SITE_8R_A>(args, src, as + (i * NW + wid) * 8 * BK, smem, SMEM_MAIN, fs.base, fs.end);
+      else dma16<SITE_8R_A>(args, src, as + (i * NW + wid) * 8 * BK, smem, SMEM_MAIN);
     }
 #pragma unroll
     for (int i = 0; i < IBL; ++i) dma16<SITE_8R_B>(args, fb[i], bs + (i * NW + wid) * 8 * BK, smem, SMEM_MAIN);
@@ -378,12 +380,7 @@ __global__ __launch_bounds__(512, 1) void gemm8r_kernel(const GemmArgs args) {
 #pragma unroll
     for (int i = 0; i <= IBL; ++i) fb[i] += BK;  // the zero page is large enough for the running offset
     if constexpr (CONV) {
-      f_c += BK;
-      if (f_c == args.Cin) {
-        f_c = 0;
-        if (++f_kx == args.kw) { f_kx = 0; ++f_ky; }
-        set_rows();
-      }
+      if (conv_walk_step<XS>(args, fw)) set_rows();
     } else {
 #pragma unroll
       for (int i = 0; i < IA; ++i) fa[i] += BK;
@@ -446,7 +443,9 @@ static int launch8r(const GemmArgs& a0, int ksplit, bool conv, hipStream_t s) {
   a.gn_seg = gn_seg_for<256, BN, 4>();
   const int tiles = ((a.M + 255) / 256) * ((a.N + BN - 1) / BN);
   dim3 grid(tiles, ksplit);
-  if (conv)
+  if (conv && a.xs_n)
+    gemm8r_kernel<BN, S, true, true><<<grid, 512, 0, s>>>(a);
+  else if (conv)
     gemm8r_kernel<BN, S, true><<<grid, 512, 0, s>>>(a);
   else
     gemm8r_kernel<BN, S, false><<<grid, 512, 0, s>>>(a);
@@ -480,6 +479,9 @@ int csk_gemm8p_launch(const GemmArgs& a, int tile, int ksplit, bool conv, hipStr
                     (!conv || (size_t)(a.Cin + BK) * sizeof(bf16_t) <= (size_t)csk_zero_bytes());
   if (!fast || a.ln_part || a.row_part) return (int)hipErrorNotSupported;
   if (tile == 33 && a.act == ACT_GEGLU) return (int)hipErrorNotSupported;  // 80 columns per wave: no GEGLU pairing
+  // extra K segments: the ring kernel only (the phased kernel sits at its 256-register
+  // budget and is not extended); an error, not a fallback
+  if (a.xs_n && (!conv || tile == 31 || tile == 32)) return (int)hipErrorInvalidValue;
   switch (tile) {
     case 33: return launch8r<160, 3>(a, ksplit, conv, s);
     case 34: return launch8r<128, 3>(a, ksplit, conv, s);  // 64 x 64 per wave: direct row-layout epilogue

@@ -126,6 +126,17 @@ struct GemmArgs {
   float* fx_ws;
   unsigned* fx_cnt;
   int fx_split;
+  // extra K segments of an implicit-GEMM conv (csk_conv2d_ex2 / csk_conv2d_gn2:
+  // a ResNet's 1x1 shortcut folded into its conv2): after the kh * kw taps the K
+  // loop walks xs_n more sources, each an NHWC bf16 tensor of the OUTPUT's
+  // [B][Ho][Wo] with xs_c[i] channels at pixel stride xs_ld[i]; a row reads its
+  // own output pixel.  K = kh * kw * Cin + sum xs_c, W = [N][K].  FAST staging
+  // of the LDS-DMA kernels only (stride 1, no up2x, Ho x Wo == H x W, every
+  // channel count a multiple of BK); xs_end: one past the last readable element
+  const bf16_t* xs_ptr[2];
+  const bf16_t* xs_end[2];
+  int xs_ld[2], xs_c[2];
+  int xs_n;
 };
 
 #define ZERO_BYTES (128 * 1024)  // the LDS-DMA zero page (gemm_glds.hip: csk_init)
@@ -141,13 +152,17 @@ typedef __attribute__((address_space(3))) void* csk_lptr_t;
 // One 16-byte-per-lane LDS-DMA (a wave writes 1 KB at dst).  CSK_DEBUG builds
 // check each lane's source against the operand extents (A, W or the zero page)
 // and the wave's destination against the workgroup's LDS array.
+// alo / ahi: the tensor the A operand is staged from at this K-step where that
+// is not args.A (an extra K segment while it is active, ConvSrc base / end)
 template <int SITE>
 __device__ __forceinline__ void dma16(const GemmArgs& args, const bf16_t* src, bf16_t* dst, const bf16_t* lds,
-                                      int lds_elems) {
+                                      int lds_elems, const bf16_t* alo = nullptr, const bf16_t* ahi = nullptr) {
 #ifdef CSK_DEBUG
-  const bool ok = (src >= args.A && src + 8 <= args.a_end) || (src >= args.W && src + 8 <= args.w_end) ||
+  const bf16_t* a0 = alo ? alo : args.A;
+  const bf16_t* a1 = alo ? ahi : args.a_end;
+  const bool ok = (src >= a0 && src + 8 <= a1) || (src >= args.W && src + 8 <= args.w_end) ||
                   (src >= args.zero && src + 8 <= args.zero + ZERO_BYTES / 2);
-  CSK_DCHECK(ok, SITE, src - args.A, args.a_end - args.A);
+  CSK_DCHECK(ok, SITE, src - a0, a1 - a0);
   const long long off = dst - lds;
   CSK_DCHECK(off >= 0 && off + 512 <= lds_elems, SITE + 100, off, lds_elems);
 #endif
@@ -171,6 +186,100 @@ constexpr int epi_smem_elems() {
 }
 
 #define BK 64
+
+// The wave-uniform walk over a FAST conv's K dimension (SGPR state): tap
+// (ky, kx) and channel offset c inside it; XS kernels go on through the extra
+// segments (seg >= 0) after the last tap.  cn: channels of the current tap /
+// segment (the wrap test).
+struct ConvWalk {
+  int ky, kx, c, cn, seg;
+};
+
+// position of K offset kbeg (a multiple of BK; channel counts are too, so it
+// never lands inside a K-step): inside a tap, exactly on the tap-to-segment
+// boundary, or inside / on the start of a segment
+template <bool XS>
+__device__ __forceinline__ ConvWalk conv_walk_begin(const GemmArgs& args, int kbeg) {
+  ConvWalk w;
+  w.seg = -1;
+  w.cn = args.Cin;
+  const int ktaps = args.kh * args.kw * args.Cin;
+  if (XS && kbeg >= ktaps) {
+    int r = kbeg - ktaps;
+    w.seg = 0;
+    if (r >= args.xs_c[0]) {
+      r -= args.xs_c[0];
+      w.seg = 1;
+    }
+    w.cn = w.seg == 0 ? args.xs_c[0] : args.xs_c[1];
+    w.c = r;
+    w.ky = args.kh;
+    w.kx = 0;
+    return w;
+  }
+  const int tap = kbeg / args.Cin;
+  w.c = kbeg - tap * args.Cin;
+  w.ky = tap / args.kw;
+  w.kx = tap - w.ky * args.kw;
+  return w;
+}
+
+// one K-step further; true when the tap / segment changed (the caller
+// recomputes its row pointers)
+template <bool XS>
+__device__ __forceinline__ bool conv_walk_step(const GemmArgs& args, ConvWalk& w) {
+  w.c += BK;
+  if (w.c != w.cn) return false;
+  w.c = 0;
+  if constexpr (XS) {
+    if (w.seg >= 0) {
+      ++w.seg;
+    } else if (++w.kx == args.kw) {
+      w.kx = 0;
+      if (++w.ky == args.kh) w.seg = 0;
+    }
+    if (w.seg >= 0) w.cn = w.seg == 0 ? args.xs_c[0] : args.xs_c[1];
+  } else {
+    if (++w.kx == args.kw) {
+      w.kx = 0;
+      ++w.ky;
+    }
+  }
+  return true;
+}
+
+// The A source of the walk's current position: the conv input shifted by the
+// tap, or (XS) the segment's tensor at the output pixel itself, i.e. the centre
+// tap's (ih, iw) = (oh, ow) at stride 1.  ok is false past the last segment
+// (the step after the K loop's last one): every row then points at the zero page.
+struct ConvSrc {
+  const bf16_t* base;
+  const bf16_t* end;
+  int ld, dy, dx;
+  bool ok;
+};
+template <bool XS>
+__device__ __forceinline__ ConvSrc conv_walk_src(const GemmArgs& args, const ConvWalk& w) {
+  ConvSrc s;
+  s.base = args.A;
+  s.end = args.a_end;
+  s.ld = args.lda;
+  s.dy = w.ky * args.dil;
+  s.dx = w.kx * args.dil;
+  s.ok = true;
+  if constexpr (XS) {
+    if (w.seg >= 0) {
+      const int q = w.seg == 0 ? 0 : 1;
+      s.base = args.xs_ptr[q];
+      s.end = args.xs_end[q];
+      s.ld = args.xs_ld[q];
+      s.dy = args.pt;
+      s.dx = args.pl;
+      s.ok = w.seg < args.xs_n;
+    }
+  }
+  return s;
+}
 
 // zero page owned by gemm_glds.hip (allocated by csk_init): LDS-DMA padding
 // source and the FAST staging paths' pointer target for invalid rows / taps

@@ -42,7 +42,11 @@ constexpr int glds_min_waves() {
   return (BN == 160 && BM <= 128) ? 2 : 1;
 }
 
-template <int BM, int BN, int WM, int WN, int S, bool CONV, bool FAST, bool ATTN = false, bool FX = false>
+// XS (FAST convs): the K loop goes on through GemmArgs' extra segments after
+// the last tap (gemm_common.h ConvWalk); a separate instance, so the plain
+// convs keep their code and registers
+template <int BM, int BN, int WM, int WN, int S, bool CONV, bool FAST, bool ATTN = false, bool FX = false,
+          bool XS = false>
 __global__ __launch_bounds__(256, (glds_min_waves<BM, BN>())) void gemm_glds_kernel(const GemmArgs args) {
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int MT = WTM / 16, NT = WTN / 16;
@@ -118,24 +122,23 @@ __global__ __launch_bounds__(256, (glds_min_waves<BM, BN>())) void gemm_glds_ker
   // ---- FAST path state: per-row running source pointers, uniform tap / channel offset ----
   const bf16_t* fa[IA];
   const bf16_t* fb[IB];
-  int f_ky = 0, f_kx = 0, f_c = 0;
+  ConvWalk fw{0, 0, 0, args.Cin, -1};
+  ConvSrc fs{args.A, args.a_end, args.lda, 0, 0, true};
   auto set_rows = [&]() {
+    fs = conv_walk_src<XS>(args, fw);
 #pragma unroll
     for (int i = 0; i < IA; ++i) {
-      const int ih = a_ihb[i] + f_ky * args.dil, iw = a_iwb[i] + f_kx * args.dil;
-      const bool v = a_ok[i] && ih >= 0 && ih < Hin && iw >= 0 && iw < Win;
+      const int ih = a_ihb[i] + fs.dy, iw = a_iwb[i] + fs.dx;
+      const bool v = fs.ok && a_ok[i] && ih >= 0 && ih < Hin && iw >= 0 && iw < Win;
       const int sh = args.up2x ? (ih >> 1) : ih, sw = args.up2x ? (iw >> 1) : iw;
-      fa[i] = v ? args.A + (a_bbase[i] + (size_t)sh * args.Wd + sw) * args.lda + lchunk * 8 : zero + lchunk * 8;
+      fa[i] = v ? fs.base + (a_bbase[i] + (size_t)sh * args.Wd + sw) * fs.ld + lchunk * 8 : zero + lchunk * 8;
     }
   };
   if constexpr (FAST) {
 #pragma unroll
     for (int i = 0; i < IB; ++i) fb[i] = b_ok[i] ? b_ptr[i] : zero + lchunk * 8;
     if constexpr (CONV) {
-      const int tap = kbeg / args.Cin;
-      f_c = kbeg - tap * args.Cin;
-      f_ky = tap / args.kw;
-      f_kx = tap - f_ky * args.kw;
+      fw = conv_walk_begin<XS>(args, kbeg);
       set_rows();
     } else {
 #pragma unroll
@@ -147,11 +150,12 @@ __global__ __launch_bounds__(256, (glds_min_waves<BM, BN>())) void gemm_glds_ker
     bf16_t* as = smem + buf * STAGE;
     bf16_t* bs = as + BM * BK;
     if constexpr (FAST) {
-      if (!(CONV && S == 2 && args.act == ACT_PROBE_NO_A && f_kx != 0)) {
+      if (!(CONV && S == 2 && args.act == ACT_PROBE_NO_A && fw.kx != 0)) {
 #pragma unroll
         for (int i = 0; i < IA; ++i) {
-          const bf16_t* src = CONV ? fa[i] + f_c : fa[i];
-          dma16<SITE_GLDS_A>(args, src, as + (wid * IA + i) * 8 * BK, smem, SMEM);
+          const bf16_t* src = CONV ? fa[i] + fw.c : fa[i];
+          if constexpr (XS) dma16<SITE_GLDS_A>(args, src, as + (wid * IA + i) * 8 * BK, smem, SMEM, fs.base, fs.end);
+          else dma16<SITE_GLDS_A>(args, src, as + (wid * IA + i) * 8 * BK, smem, SMEM);
         }
       }
 #pragma unroll
@@ -160,12 +164,7 @@ __global__ __launch_bounds__(256, (glds_min_waves<BM, BN>())) void gemm_glds_ker
         fb[i] += BK;
       }
       if constexpr (CONV) {
-        f_c += BK;
-        if (f_c == args.Cin) {
-          f_c = 0;
-          if (++f_kx == args.kw) { f_kx = 0; ++f_ky; }
-          set_rows();
-        }
+        if (conv_walk_step<XS>(args, fw)) set_rows();
       } else {
 #pragma unroll
         for (int i = 0; i < IA; ++i) fa[i] += BK;
@@ -328,6 +327,11 @@ static int launch_glds(const GemmArgs& a0, int ksplit, bool conv, hipStream_t s)
                     (size_t)(span + 2 * BK) * sizeof(bf16_t) <= ZERO_BYTES &&
                     (!conv || (size_t)(a.Cin + BK) * sizeof(bf16_t) <= ZERO_BYTES);
   dim3 grid(tiles, ksplit);
+  if (a.xs_n) {  // extra K segments (csk_conv2d_ex2 checked the geometry): FAST conv staging, reduce-kernel split-K
+    if (!conv || !fast || a.attn_kv || a.fx_cnt) return (int)hipErrorInvalidValue;
+    gemm_glds_kernel<BM, BN, WM, WN, S, true, true, false, false, true><<<grid, 256, 0, s>>>(a);
+    return (int)hipGetLastError();
+  }
   if (a.attn_kv) {  // the query projection with the attention epilogue (csk_gemm_ln_attn)
     if constexpr (BM == 128 && BN == 64 && WM == 4 && WN == 1) {
       if (conv || !fast || ksplit != 1) return (int)hipErrorInvalidValue;

@@ -28,6 +28,8 @@ from chiaswarm_amd.ops import _lib, hip_ops  # noqa: E402
 def apply_arm(arm):
     if arm in ("side0", "side1"):  # ResNet shortcuts on a forked side stream (1) or inline (0)
         ops.SIDE_STREAM = arm == "side1"
+    elif arm in ("scf0", "scf1"):  # ResNet 1x1 shortcuts: own GEMMs + residual (0) / extra K segments of conv2 (1)
+        ops.SC_FUSE = arm == "scf1"
     elif arm in ("swodd0", "swodd1"):  # 160-wide tiles: LDS (0) / direct row-layout (1) epilogue
         _lib.call("csk_set_sw_odd", int(arm == "swodd1"))
     elif arm in ("nt0", "nt1", "nt2"):  # direct epilogue: plain / non-temporal C stores (/ + residual loads);
@@ -113,6 +115,7 @@ def main():
     ctx = torch.randn(a.batch, 77, 1024, device=dev).bfloat16()
     kv = p.unet.encode_context(ctx)
     graphs = {}
+    hold = []  # packed weights an arm's graph reads: a later arm (scf1) may release a module's copy
     for arm in a.arms.split(","):
         # combined knobs, e.g. gcm2+gcb1024 (settings persist into later arms); "arm@tag"
         # repeats an arm under another name: the spread between identical arms
@@ -128,6 +131,7 @@ def main():
             for (b, h, w, ci, co, sp, raw), k in sorted(sites.items()):
                 print(f"    {k} x conv {b}x{h}x{w} {ci} -> {co} split {sp} {'conv2 (raw kept)' if raw else 'conv1'}", flush=True)
         hip_ops.SKGN_SITES = None
+        hold.append([m.__dict__.get("wp") for m in p.unet.modules()])
     res = {arm: [] for arm in graphs}
     for _ in range(a.rounds):
         for arm, g in graphs.items():

@@ -4,6 +4,7 @@ for PMC counter runs and tile A/Bs:
 
     python tools/convbench.py --shape 8,64,64,320,320 --tiles 11,19,25 --iters 50
     python tools/convbench.py --gemm 32768,1280,320 --tiles 11,25
+    python tools/convbench.py --shortcut [--batch 8]   # fused conv2 vs conv2 + shortcut GEMMs, the 14 SD2.1 sites
     rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA ... -- python3 tools/convbench.py --tiles 11 --iters 5
 """
 import argparse
@@ -19,6 +20,85 @@ from chiaswarm_amd.ops import _lib  # noqa: E402
 from chiaswarm_amd.ops.hip_ops import _p, _s  # noqa: E402
 
 
+# SD2.1 ResNets with a 1x1 shortcut at 64x64 latents: (H = W, shortcut sources, Cout); 2 down, 12 up
+SD21_SHORTCUTS = [(32, (320,), 640), (16, (640,), 1280),
+                  (8, (1280, 1280), 1280), (8, (1280, 1280), 1280), (8, (1280, 1280), 1280),
+                  (16, (1280, 1280), 1280), (16, (1280, 1280), 1280), (16, (1280, 640), 1280),
+                  (32, (1280, 640), 640), (32, (640, 640), 640), (32, (640, 320), 640),
+                  (64, (640, 320), 320), (64, (320, 320), 320), (64, (320, 320), 320)]
+
+
+def _graph_us(fn, iters):
+    """device time of fn() per call: iters calls captured in one hipGraph, replayed"""
+    fn()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(iters):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) / iters * 1000)
+    return sorted(ts)[len(ts) // 2]
+
+
+def shortcut_bench(batch, iters):
+    """conv2 with the shortcut as extra K segments against conv2 (shortcut as its
+    residual) + the shortcut GEMM(s), each with its tuned plan, per distinct site"""
+    from chiaswarm_amd.ops import hip_ops
+
+    dev = "cuda"
+    seen, tot_u, tot_f = {}, 0.0, 0.0
+    for H, srcs, cout in SD21_SHORTCUTS:
+        key = (H, srcs, cout)
+        if key not in seen:
+            r = lambda *sh, sc=1.0: (torch.randn(*sh, device=dev) * sc).bfloat16()  # noqa: E731
+            h = r(batch, H, H, cout)
+            xs = [r(batch, H, H, c) for c in srcs]
+            K = 9 * cout + sum(srcs)
+            wp = ops.pack_conv_weight(r(cout, cout, 3, 3, sc=K ** -0.5))
+            wsc = r(cout, sum(srcs), sc=K ** -0.5)
+            bias = r(cout)
+            _, wv, (wf,) = ops.pack_conv_extra(wp, [wsc])
+            extra, off = [], 0
+            for t, c in zip(xs, srcs):
+                extra.append((t, wf[:, off:off + c]))
+                off += c
+            extra = tuple(extra)
+
+            def unfused():
+                sc = hip_ops.gemm(xs[0].view(-1, srcs[0]), wsc[:, :srcs[0]], bias if len(xs) == 1 else None)
+                if len(xs) > 1:
+                    sc = hip_ops.gemm(xs[1].view(-1, srcs[1]), wsc[:, srcs[0]:], bias, residual=sc)
+                return hip_ops.conv2d(h, wp, bias, 1, 1, sc.view(batch, H, H, cout), False, None, gn_stats=True)
+
+            def fused():
+                return hip_ops.conv2d(h, wv, bias, 1, 1, None, False, None, gn_stats=True, extra=extra)
+
+            seen[key] = (_graph_us(unfused, iters), _graph_us(fused, iters))
+        u, f = seen[key]
+        tot_u += u
+        tot_f += f
+    for (H, srcs, cout), (u, f) in seen.items():
+        n = sum(1 for s in SD21_SHORTCUTS if s == (H, srcs, cout))
+        print(f"{n} x {H:2d}x{H:<2d} conv2 {cout:4d} + shortcut {'|'.join(map(str, srcs)):9s}: conv2 + GEMMs {u:7.1f} us  "
+              f"fused {f:7.1f} us  ({f - u:+6.1f})", flush=True)
+    print(f"per step (14 sites, batch {batch}): conv2 + GEMMs {tot_u:7.1f} us  fused {tot_f:7.1f} us  "
+          f"({tot_f - tot_u:+6.1f})", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="8,64,64,320,320", help="B,H,W,Cin,Cout (3x3, pad 1)")
@@ -28,9 +108,14 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--act", type=int, default=0, help="GEMM epilogue activation code (3 = GEGLU, N = 2 x out)")
+    ap.add_argument("--shortcut", action="store_true",
+                    help="the 14 SD2.1 ResNet shortcut sites: conv2 with extra K segments vs conv2 + shortcut GEMMs")
+    ap.add_argument("--batch", type=int, default=8, help="--shortcut: UNet batch (CFG: 2 x images)")
     a = ap.parse_args()
     _lib.load()
     dev = "cuda"
+    if a.shortcut:
+        return shortcut_bench(a.batch, a.iters)
     if a.gemm:
         M, N, K = map(int, a.gemm.split(","))
         x = torch.randn(M, K, device=dev).bfloat16()

@@ -39,6 +39,13 @@ def flops_of(name, a):
         Ho, Wo, up = a[17], a[18], a[19]
         return (f"conv+gn B{B} {H}x{W}{' up2x' if up else ''} s{stride} {Cin}->{Cout} k{kh}{' +raw' if a[34] else ''}",
                 2.0 * B * Ho * Wo * Cout * kh * kw * Cin, a[25])
+    if name in ("csk_conv2d_ex2", "csk_conv2d_gn2"):  # conv with extra K segments (a fused ResNet shortcut)
+        B, H, W, Cin, Cout, kh, kw, stride = a[7:15]
+        ca, cb = a[-5], a[-2]
+        gn = name == "csk_conv2d_gn2"
+        return (f"conv{'+gn' if gn else ''} B{B} {H}x{W} s{stride} {Cin}->{Cout} k{kh} +x{ca}{'|%d' % cb if cb else ''}"
+                f"{' +raw' if gn and a[34] else ''}",
+                2.0 * B * H * W * Cout * (kh * kw * Cin + ca + cb), a[25] if gn else a[-10])
     if name == "csk_attention":
         B, H, Sq, Skv, D = a[5:10]
         return f"attn B{B} H{H} Sq{Sq} Skv{Skv} D{D}", 4.0 * B * H * Sq * Skv * D, None

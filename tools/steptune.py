@@ -89,12 +89,24 @@ def main():
     used = {}
     orig_choose = tuning.choose
 
-    def spy(key, M, N, K, runner):
-        r = orig_choose(key, M, N, K, runner)
+    def spy(key, M, N, K, runner, *rest):
+        r = orig_choose(key, M, N, K, runner, *rest)
         used.setdefault(key, (M, N, K, r))
         return r
 
+    # convs with extra K segments (fused ResNet shortcuts): their own keys, only
+    # the tiles that walk the segments, split through the reduce kernel
+    only_tiles = {}
+    orig_extra = tuning.choose_extra
+
+    def spy_extra(key, like, M, N, K, runner, tiles):
+        r = orig_extra(key, like, M, N, K, runner, tiles)
+        used[key] = (M, N, K, r)  # (replaces what the inner choose() recorded on a table hit)
+        only_tiles[key] = tiles
+        return r
+
     tuning.choose = spy
+    tuning.choose_extra = spy_extra
     table = tuning.table()
     present0 = set(table)  # keys present before the first capture
 
@@ -137,7 +149,8 @@ def main():
         tkey = f"{a.context}|{key}" if a.context else key  # the table entry this run writes
         only = {int(v) for v in a.only_tiles.split(",") if v}
         cands = [c for c in tuning.candidates(M, N, K) if (a.all_tiles or c[0] in SHORTLIST) and c != tuple(cur)
-                 and (not only or c[0] in only)]
+                 and (not only or c[0] in only)
+                 and (key not in only_tiles or (c[0] in only_tiles[key] and c[1] > 0))]
         if a.fixup:  # the current tile with every fixup split, and the current split's fixup on the 64-wide tiles
             cs = abs(int(cur[1]))
             cands = [c for c in cands if c[1] < 0 and (c[0] == int(cur[0]) or (cs > 1 and c[1] == -cs
