@@ -34,6 +34,7 @@ traffic.  The original-T5 (ReLU FFN) language models are refused.
 from __future__ import annotations
 
 import dataclasses
+import os
 
 import numpy as np
 import torch
@@ -347,13 +348,14 @@ class Blip2Captioner(nn.Module):
 
     @torch.no_grad()
     def generate(self, image: Image.Image, prefix_ids: list[int], max_new_tokens: int | None = None,
-                 max_length: int = 20, qtext_ids: list[int] | None = None) -> list[int]:
+                 max_length: int = 20, qtext_ids: list[int] | None = None, use_cache: bool | None = None) -> list[int]:
         """Greedy decode from ``</s> + prefix`` after the image queries; returns
-        prefix + generated ids (without the leading ``</s>``)."""
+        prefix + generated ids (without the leading ``</s>``).  ``use_cache``
+        (Vicuna-LLaMA only): see ``_generate_llama``."""
         if self.cfg.lm_type == "t5":
             return self._generate_t5(image, prefix_ids, max_new_tokens, max_length, qtext_ids)
         if self.cfg.lm_type == "llama":
-            return self._generate_llama(image, prefix_ids, max_new_tokens, max_length, qtext_ids)
+            return self._generate_llama(image, prefix_ids, max_new_tokens, max_length, qtext_ids, use_cache)
         if max_new_tokens is None:
             max_new_tokens = max(0, max_length - 1 - len(prefix_ids))
         prefix = self.image_prefix(self.preprocess(image).to(self.embed_tokens.weight.device))
@@ -389,22 +391,44 @@ class Blip2Captioner(nn.Module):
             ids.append(nxt)
         return ids[1:]
 
-    def _generate_llama(self, image, prompt_ids, max_new_tokens, max_length, qtext_ids=None) -> list[int]:
+    def _generate_llama(self, image, prompt_ids, max_new_tokens, max_length, qtext_ids=None,
+                        use_cache=None) -> list[int]:
         """InstructBLIP (Vicuna): greedy decode after [queries; <s> prompt];
-        returns the generated ids."""
+        returns the generated ids.  One ``prefill`` of the prompt, then one
+        KV-cached ``decode_step`` per token.  ``use_cache=False`` (or
+        ``CSK_DECODE=0`` in the environment when it is left at None) re-runs the
+        whole sequence through ``last_logits`` for every token instead."""
         if max_new_tokens is None:
             max_new_tokens = max(0, max_length - 1)
-        emb = self.llama.model.embed_tokens
+        if use_cache is None:
+            use_cache = os.environ.get("CSK_DECODE", "1") == "1"
+        lm = self.llama
+        emb = lm.model.embed_tokens
         prefix = self.image_prefix(self.preprocess(image).to(emb.weight.device), qtext_ids)
         ids = [self.cfg.bos_id] + list(prompt_ids)
         out = []
-        for _ in range(max_new_tokens):
-            x = torch.cat([prefix, emb(torch.tensor([ids], device=prefix.device)).to(prefix.dtype)], 1)
-            nxt = int(self.llama.last_logits(x).argmax())
+        if not use_cache:
+            for _ in range(max_new_tokens):
+                x = torch.cat([prefix, emb(torch.tensor([ids], device=prefix.device)).to(prefix.dtype)], 1)
+                nxt = int(lm.last_logits(x).argmax())
+                if nxt == self.cfg.eos_id:
+                    break
+                ids.append(nxt)
+                out.append(nxt)
+            return out
+        if max_new_tokens == 0:
+            return out
+        x = torch.cat([prefix, emb(torch.tensor([ids], device=prefix.device)).to(prefix.dtype)], 1)
+        n = x.shape[1]
+        lm.new_cache(n + max_new_tokens)
+        logits = lm.prefill(x)
+        for i in range(max_new_tokens):
+            nxt = int(logits.argmax())
             if nxt == self.cfg.eos_id:
                 break
-            ids.append(nxt)
             out.append(nxt)
+            if i + 1 < max_new_tokens:
+                logits = lm.decode_step(nxt, n + i)
         return out
 
 

@@ -1003,44 +1003,109 @@ def attention(q, k, v, scale=None, causal=False, kv_len=None, *, bias=None, kv_l
 # ----------------------------------------------------------------------------
 # KV-cached decode: one token (or a few rows) per step
 # ----------------------------------------------------------------------------
-def gemv(x, w, bias=None, *, act=None, residual=None, ln=None, out=None):
-    """y[..., N] = act(LayerNorm?(x)[..., K] @ w[N, K]^T + bias) + residual for the
-    handful of rows of a decode step; ``ln = (gamma, beta, eps)`` normalises the
-    rows first.  Defined as ``gemm(layer_norm(x, *ln), w, bias, residual=, act=)``,
+def _ref_rms_norm(x, gamma, eps):
+    """fp32 RMSNorm of the last dim (models/llama.py RMSNorm), not rounded"""
+    xf = x.float()
+    return xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * gamma.float()
+
+
+def _ref_decode_norm(x2, ln, rms, what):
+    if ln is not None and rms is not None:
+        raise ValueError(f"{what}: ln= and rms= exclude each other")
+    if ln is not None:
+        return _ref_layer_norm(x2, ln[0], ln[1], ln[2])
+    if rms is not None:
+        return _ref_rms_norm(x2, rms[0], rms[1]).to(_cdt(x2))
+    return x2
+
+
+def gemv(x, w, bias=None, *, act=None, residual=None, ln=None, rms=None, out=None):
+    """y[..., N] = act(norm?(x)[..., K] @ w[N, K]^T + bias) + residual for the
+    handful of rows of a decode step; ``ln = (gamma, beta, eps)`` LayerNorms the
+    rows first, ``rms = (gamma, eps)`` RMSNorms them (one of the two at most).
+    Defined as ``gemm(layer_norm(x, *ln), w, bias, residual=, act=)``, resp.
+    ``gemm(x.float() * rsqrt(mean(x.float()**2, -1) + eps) * gamma.float(), ...)``,
     which is what runs on the CPU and in reference mode.  On the HIP path up to 8
-    rows go to the weight-streaming GEMV kernel (LayerNorm in its prologue);
-    more rows, K not a multiple of 8 or a GEGLU activation run layer_norm + gemm.
+    rows go to the weight-streaming GEMV kernel (the norm in its prologue, the
+    normalised rows never rounded); more rows, K not a multiple of 8 or a GEGLU
+    activation run layer_norm / a torch RMSNorm + gemm.
     ``out``: optional [rows, N] view (contiguous last dim) to write into."""
+    if ln is not None and rms is not None:
+        raise ValueError("gemv: ln= and rms= exclude each other")
     lead = x.shape[:-1]
     k = x.shape[-1]
     x2 = x.reshape(-1, k)
     if use_hip(x):
         from . import hip_ops
 
-        y = hip_ops.gemv(x2, w, bias, act, residual, ln, out)
+        y = hip_ops.gemv(x2, w, bias, act, residual, ln, out, rms)
     else:
-        if ln is not None:
-            x2 = _ref_layer_norm(x2, ln[0], ln[1], ln[2])
-        y = _ref_gemm(x2, w, bias, residual, act)
+        y = _ref_gemm(_ref_decode_norm(x2, ln, rms, "gemv"), w, bias, residual, act).to(x.dtype)
         if out is not None:
             out.copy_(y)
             y = out
     return y.view(*lead, y.shape[-1]) if out is None else y
 
 
-def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=None, pos=None):
-    """One query per (b, h) over the first ``kv_len`` keys of a [B, S, H, D] KV
+def gemv_glu(x, w_gate, w_up, *, act="silu", rms=None, ln=None, out=None):
+    """Gated two-matrix projection of a decode step (SwiGLU with ``act="silu"``):
+    y[..., N] = act(x' @ w_gate[N, K]^T) * (x' @ w_up[N, K]^T), x' = x after the
+    optional ``ln`` / ``rms`` norm of ``gemv``.  The two weights stay separate
+    tensors (no interleaved or concatenated copy is made).  Defined as
+    ``apply_act(_ref_gemm(x', w_gate), act) * _ref_gemm(x', w_up)`` in the input
+    dtype (CPU / reference mode).  HIP: up to 8 rows run one launch of the GEMV
+    kernel's gated form, a wave streaming the gate row and the up row of each of
+    its columns; outside its limits, two ``gemm`` calls and a multiply.  There is
+    no bias and no residual."""
+    if ln is not None and rms is not None:
+        raise ValueError("gemv_glu: ln= and rms= exclude each other")
+    if act == "geglu":
+        raise ValueError("gemv_glu: act is the gate's pointwise activation, not 'geglu'")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, x.shape[-1])
+    if use_hip(x):
+        from . import hip_ops
+
+        y = hip_ops.gemv_glu(x2, w_gate, w_up, act, rms, ln, out)
+    else:
+        xn = _ref_decode_norm(x2, ln, rms, "gemv_glu")
+        y = (_ref_gemm(xn, w_gate, None, None, act) * _ref_gemm(xn, w_up, None, None, None)).to(x.dtype)
+        if out is not None:
+            out.copy_(y)
+            y = out
+    return y.view(*lead, y.shape[-1]) if out is None else y
+
+
+def _ref_rope(x, cos, sin):
+    """rotate-half RoPE in fp32: x [..., D], cos / sin broadcastable to [..., D / 2]"""
+    h = x.shape[-1] // 2
+    xf = x.float()
+    a, b = xf[..., :h], xf[..., h:]
+    return torch.cat((a * cos - b * sin, b * cos + a * sin), -1)
+
+
+def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=None, pos=None, rope=None):
+    """One query per (b, h) over the first ``kv_len`` keys of a [B, S, Hkv, D] KV
     cache; returns [B, 1, H, D].  ``kv_len``: int32 [1] tensor on q's device,
     clamped to [0, S] (0 gives zeros); on the HIP path the kernel reads it, so
-    the call is hipGraph-capturable.  With ``k_new`` / ``v_new`` ([B, 1, H, D]
+    the call is hipGraph-capturable.  With ``k_new`` / ``v_new`` ([B, 1, Hkv, D]
     views, e.g. slices of the QKV projection) the new token's key and value are
     first written into the caches at index kv_len - 1.
 
-    Definition (CPU / reference): that write, then ``_ref_attention`` over the
-    first kv_len keys.  HIP: the split-KV decode kernel with the append fused in
-    for D in {32, 64, 128}; other head dims run index_copy_ + ``attention(kv_len=)``
-    (``pos``: optional long [1] device tensor holding kv_len - 1 for that
-    index_copy_, so a caller that has it spares the fallback deriving it)."""
+    Grouped heads: ``Hkv`` divides ``H``; query head h reads K/V head
+    h // (H // Hkv).  ``rope = (cos, sin)``: fp32 [P, D / 2] tables on the device
+    (P >= S), row kv_len - 1: the query and the new key are rotated (rotate-half
+    form, fp32) before use; the rotated key, rounded to the cache dtype, is what
+    is stored and scored, so the caches hold post-RoPE keys.  ``v_new`` is not
+    touched; without ``k_new`` only the query is rotated.
+
+    Definition (CPU / reference): the rotation, that write, the K/V heads
+    expanded to the query heads, then ``_ref_attention`` over the first kv_len
+    keys.  HIP: the split-KV decode kernel with all of it fused in for D in
+    {32, 64, 128}; other head dims do the same steps in torch around
+    ``attention(kv_len=)`` (``pos``: optional long [1] device tensor holding
+    kv_len - 1 for that index_copy_, so a caller that has it spares the fallback
+    deriving it)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.device != q.device:
@@ -1048,25 +1113,37 @@ def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=No
     if q.dim() != 4 or q.shape[1] != 1:
         raise ValueError(f"decode_attention: q must be [B, 1, H, D], got {tuple(q.shape)}")
     B, _, H, D = q.shape
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[2:] != (H, D):
+    if (k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[0] != B or k_cache.shape[3] != D
+            or k_cache.shape[2] < 1 or H % k_cache.shape[2] != 0):
         raise ValueError(f"decode_attention: caches {tuple(k_cache.shape)} / {tuple(v_cache.shape)} do not match "
                          f"q {tuple(q.shape)}")
+    Hkv = k_cache.shape[2]
     if (k_new is None) != (v_new is None):
         raise ValueError("decode_attention: k_new and v_new come together")
-    if k_new is not None and (k_new.shape != q.shape or v_new.shape != q.shape):
+    if k_new is not None and (k_new.shape != (B, 1, Hkv, D) or v_new.shape != (B, 1, Hkv, D)):
         raise ValueError(f"decode_attention: k_new / v_new {tuple(k_new.shape)} / {tuple(v_new.shape)} must be "
-                         f"{tuple(q.shape)}")
+                         f"{(B, 1, Hkv, D)}")
+    if rope is not None and (D % 2 or len(rope) != 2):
+        raise ValueError("decode_attention: rope = (cos, sin) needs an even head dim")
     if use_hip(q):
         from . import hip_ops
 
-        return hip_ops.decode_attention(q, k_cache, v_cache, scale, kv_len, k_new, v_new, pos)
+        return hip_ops.decode_attention(q, k_cache, v_cache, scale, kv_len, k_new, v_new, pos, rope)
     n = min(max(int(kv_len.reshape(-1)[0].item()), 0), k_cache.shape[1])
-    if k_new is not None and n > 0:
-        k_cache[:, n - 1] = k_new[:, 0].to(k_cache.dtype)
-        v_cache[:, n - 1] = v_new[:, 0].to(v_cache.dtype)
     if n == 0:
         return torch.zeros_like(q)
-    return _ref_attention(q, k_cache[:, :n], v_cache[:, :n], scale, False)
+    if rope is not None:
+        cos, sin = rope[0][n - 1].float(), rope[1][n - 1].float()
+        q = _ref_rope(q, cos, sin).to(q.dtype)
+        if k_new is not None:
+            k_new = _ref_rope(k_new, cos, sin)
+    if k_new is not None:
+        k_cache[:, n - 1] = k_new[:, 0].to(k_cache.dtype)
+        v_cache[:, n - 1] = v_new[:, 0].to(v_cache.dtype)
+    k, v = k_cache[:, :n], v_cache[:, :n]
+    if Hkv != H:
+        k, v = (t[:, :, :, None].expand(B, n, Hkv, H // Hkv, D).reshape(B, n, H, D) for t in (k, v))
+    return _ref_attention(q, k, v, scale, False)
 
 
 # ----------------------------------------------------------------------------

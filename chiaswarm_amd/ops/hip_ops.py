@@ -1359,16 +1359,23 @@ def xin_qkv(x, stat, gamma, beta, w, bi, colsum, bq, eps):
 # split-KV attention with the K/V append fused in (csrc/kernels/attn_decode.hip).
 # Called only where decode code asks for them (ops.gemv / ops.decode_attention):
 # ops.gemm / ops.attention dispatch as before.  CSK_DECODE=0 / set_decode(False):
-# both ops take their fallback (layer_norm + gemm; index_copy_ x2 + attention).
+# both ops take their fallback (layer_norm / RMSNorm + gemm; index_copy_ x2 + attention).
 # ---------------------------------------------------------------------------
 sig("csk_gemv", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
     c_int, c_int, c_int, c_int, c_float, c_void_p)
+sig("csk_gemv_ex", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p)
+sig("csk_gemv_plan", c_int)
 sig("csk_set_gemv_nt", c_int)
 sig("csk_attention_decode", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
     c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p)
+sig("csk_attention_decode_ex", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+    c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p)
 sig("csk_attn_decode_split")
 DECODE = os.environ.get("CSK_DECODE", "1") == "1"
-DECODE_STATS = {"gemv": 0, "decode_attention": 0}  # kernel launches per op (tests assert the kernels ran)
+# kernel launches per op (tests assert the kernels ran)
+DECODE_STATS = {"gemv": 0, "decode_attention": 0, "gemv_glu": 0}
+GEMV_NORM_NONE, GEMV_NORM_LN, GEMV_NORM_RMS = 0, 1, 2  # gemv.hip GV_NORM_*
 GEMV_MAX_M = 8             # gemv.hip GV_MAX_M
 GEMV_LDS_FLOATS = 32768    # gemv.hip GV_LDS_FLOATS: padded rows x K fp32 the kernel keeps in LDS
 DECODE_SPLIT = 64          # attn_decode.hip AD_SPLIT: keys per workgroup
@@ -1396,12 +1403,47 @@ def _aligned_rows(t, single_row_ok=False):
             and (t.stride(0) % 8 == 0 or (single_row_ok and t.shape[0] == 1)))
 
 
-def gemv(x2, w, bias=None, act=None, residual=None, ln=None, out=None):
-    """y[M, N] = act(LN?(x2)[M, K] @ w[N, K]^T + bias) + residual on the GEMV
-    kernel for M <= 8; ``ln = (gamma, beta, eps)``.  ``x2``, ``residual`` and
-    ``out`` may be row-strided views, ``w`` a view whose row stride is a
-    multiple of 8.  What the kernel does not take (M > 8, K % 8, GEGLU, rows
-    beyond its LDS budget) runs layer_norm + gemm instead."""
+def rms_norm(x, gamma, eps):
+    """RMSNorm of the last dim in torch (fp32 inside, rounded to x's dtype): the
+    fallback of the GEMV's ``rms=`` prologue."""
+    from . import _ref_rms_norm
+
+    return _ref_rms_norm(x, gamma, eps).to(x.dtype)
+
+
+def _gemv_kernel_takes(M, K):
+    mt = 1 if M <= 1 else 2 if M <= 2 else 4 if M <= 4 else 8
+    return DECODE and 1 <= M <= GEMV_MAX_M and K % 8 == 0 and K >= 8 and mt * K <= GEMV_LDS_FLOATS
+
+
+def _gemv_norm(ln, rms, K):
+    """(mode, gamma, beta, eps) of the kernel's prologue"""
+    if ln is None and rms is None:
+        return GEMV_NORM_NONE, None, None, 0.0
+    if ln is not None:
+        mode, (gamma, beta, eps), what = GEMV_NORM_LN, ln, "LayerNorm"
+    else:
+        mode, (gamma, eps), beta, what = GEMV_NORM_RMS, rms, None, "RMSNorm"
+    _bf16(gamma, "gemv.gamma")
+    if gamma.numel() != K or (beta is not None and beta.numel() != K):
+        raise ValueError(f"gemv: {what} affine of {gamma.numel()} elements for K = {K}")
+    gamma = gamma.contiguous()
+    if gamma.data_ptr() % 16:
+        gamma = gamma.clone()
+    if beta is not None:
+        _bf16(beta, "gemv.beta")
+        beta = beta.contiguous()
+        if beta.data_ptr() % 16:
+            beta = beta.clone()
+    return mode, gamma, beta, float(eps)
+
+
+def gemv(x2, w, bias=None, act=None, residual=None, ln=None, out=None, rms=None):
+    """y[M, N] = act(norm?(x2)[M, K] @ w[N, K]^T + bias) + residual on the GEMV
+    kernel for M <= 8; ``ln = (gamma, beta, eps)`` or ``rms = (gamma, eps)``.
+    ``x2``, ``residual`` and ``out`` may be row-strided views, ``w`` a view whose
+    row stride is a multiple of 8.  What the kernel does not take (M > 8, K % 8,
+    GEGLU, rows beyond its LDS budget) runs layer_norm / RMSNorm + gemm instead."""
     _bf16(x2, "gemv.x")
     _bf16(w, "gemv.w")
     M, K = x2.shape
@@ -1409,10 +1451,11 @@ def gemv(x2, w, bias=None, act=None, residual=None, ln=None, out=None):
     if w.shape[1] != K:
         raise ValueError(f"gemv: K mismatch {tuple(x2.shape)} x {tuple(w.shape)}")
     code = ACT[act]
-    mt = 1 if M <= 1 else 2 if M <= 2 else 4 if M <= 4 else 8
-    if not DECODE or M < 1 or M > GEMV_MAX_M or K % 8 or K < 8 or code == 3 or mt * K > GEMV_LDS_FLOATS:
+    if not _gemv_kernel_takes(M, K) or code == 3:
         if ln is not None:
             x2 = layer_norm(x2, ln[0], ln[1], ln[2])
+        elif rms is not None:
+            x2 = rms_norm(x2, rms[0], rms[1])
         y = gemm(x2, w, bias, residual, act, out=out if out is not None and out.is_contiguous() else None)
         if out is not None and y is not out:
             out.copy_(y)
@@ -1436,25 +1479,61 @@ def gemv(x2, w, bias=None, act=None, residual=None, ln=None, out=None):
     if bias is not None:
         _bf16(bias, "gemv.bias")
         bias = bias.contiguous()
-    gamma = beta = None
-    eps = 0.0
-    if ln is not None:
-        gamma, beta, eps = ln
-        _bf16(gamma, "gemv.gamma")
-        if gamma.numel() != K or (beta is not None and beta.numel() != K):
-            raise ValueError(f"gemv: LayerNorm affine of {gamma.numel()} elements for K = {K}")
-        gamma = gamma.contiguous()
-        if gamma.data_ptr() % 16:
-            gamma = gamma.clone()
-        if beta is not None:
-            _bf16(beta, "gemv.beta")
-            beta = beta.contiguous()
-            if beta.data_ptr() % 16:
-                beta = beta.clone()
-    _lib.call("csk_gemv", _p(out), _p(x2), _p(w), _p(bias), _p(residual), _p(gamma), _p(beta), M, N, K,
-              x2.stride(0), w.stride(0), ldr, out.stride(0), code, float(eps), _s())
+    mode, gamma, beta, eps = _gemv_norm(ln, rms, K)
+    _lib.call("csk_gemv_ex", _p(out), _p(x2), _p(w), None, _p(bias), _p(residual), _p(gamma), _p(beta), mode, M, N, K,
+              x2.stride(0), w.stride(0), 0, ldr, out.stride(0), code, eps, _s())
     DECODE_STATS["gemv"] += 1
     return out
+
+
+def gemv_glu(x2, wg, wu, act="silu", rms=None, ln=None, out=None):
+    """y[M, N] = act(x' @ wg[N, K]^T) * (x' @ wu[N, K]^T), x' = norm?(x2), on the
+    gated GEMV kernel for M <= 8: both matrices are streamed where they lie (views
+    with a row stride that is a multiple of 8 are fine).  Outside the kernel's
+    limits: the norm, two ``gemm`` calls and a multiply."""
+    _bf16(x2, "gemv_glu.x")
+    _bf16(wg, "gemv_glu.w_gate")
+    _bf16(wu, "gemv_glu.w_up")
+    M, K = x2.shape
+    N = wg.shape[0]
+    if wg.shape != wu.shape or wg.shape[1] != K:
+        raise ValueError(f"gemv_glu: shapes {tuple(x2.shape)} x {tuple(wg.shape)} / {tuple(wu.shape)}")
+    code = ACT[act]
+    if code == 3:
+        raise ValueError("gemv_glu: act is the gate's pointwise activation, not 'geglu'")
+    if out is not None and (out.shape != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1
+                            or out.device != x2.device):
+        raise ValueError(f"gemv_glu: out must be a bf16 [{M}, {N}] view with a contiguous last dim")
+    if not _gemv_kernel_takes(M, K):
+        if ln is not None:
+            x2 = layer_norm(x2, ln[0], ln[1], ln[2])
+        elif rms is not None:
+            x2 = rms_norm(x2, rms[0], rms[1])
+        y = gemm(x2, wg, None, None, act) * gemm(x2, wu, None, None, None)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if not _aligned_rows(x2, single_row_ok=True):
+        x2 = x2.contiguous()
+    if not _aligned_rows(wg):
+        wg = wg.contiguous()
+    if not _aligned_rows(wu):
+        wu = wu.contiguous()
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
+    mode, gamma, beta, eps = _gemv_norm(ln, rms, K)
+    _lib.call("csk_gemv_ex", _p(out), _p(x2), _p(wg), _p(wu), None, None, _p(gamma), _p(beta), mode, M, N, K,
+              x2.stride(0), wg.stride(0), wu.stride(0), 0, out.stride(0), code, eps, _s())
+    DECODE_STATS["gemv_glu"] += 1
+    return out
+
+
+def gemv_plan(N):
+    """(columns per wave, waves per workgroup) the GEMV launcher picks for N
+    output columns, plain or gated, on the current device."""
+    v = _lib.call_int("csk_gemv_plan", int(N))
+    return v // 16, v % 16
 
 
 def _decode_ws(device, B, H, S, D):
@@ -1471,7 +1550,7 @@ def _decode_ws(device, B, H, S, D):
     return ws
 
 
-def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None):
+def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None, rope=None):
     """``ops.decode_attention`` on the HIP path (arguments validated there).
     ``pos``: the caller's long [1] device tensor holding kv_len - 1, used by the
     fallback's index_copy_ instead of deriving it from ``kv_len``."""
@@ -1481,17 +1560,35 @@ def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None)
             if t.stride(-1) != 1:
                 raise ValueError("decode_attention: last dim must be contiguous")
     B, _, H, D = q.shape
-    S = kc.shape[1]
+    S, Hkv = kc.shape[1], kc.shape[2]
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        for t in (cos, sin):
+            if t.dtype != torch.float32 or t.device != q.device or t.dim() != 2 or t.shape[1] != D // 2 \
+                    or t.shape[0] < S or not t.is_contiguous():
+                raise ValueError(f"decode_attention: rope tables must be contiguous fp32 [P >= {S}, {D // 2}] on "
+                                 f"the device of q, got {tuple(t.shape)} {t.dtype}")
 
     def vec_ok(t):
         return t is None or (t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:3]))
 
-    if not DECODE or D not in DECODE_HEAD_DIMS or B * H > 65535 or not (vec_ok(kc) and vec_ok(vc)):
+    if (not DECODE or D not in DECODE_HEAD_DIMS or B * H > 65535 or not (vec_ok(kc) and vec_ok(vc))
+            or (cos is not None and (cos.data_ptr() % 16 or sin.data_ptr() % 16))):
+        if (k_new is not None or rope is not None) and pos is None:
+            pos = (kv_len.to(torch.long) - 1).clamp_(0, S - 1)
+        if rope is not None:
+            from . import _ref_rope
+
+            c, s = cos.index_select(0, pos), sin.index_select(0, pos)  # [1, D / 2]
+            q = _ref_rope(q, c, s).to(q.dtype)
+            if k_new is not None:
+                k_new = _ref_rope(k_new, c, s).to(k_new.dtype)
         if k_new is not None:
-            if pos is None:
-                pos = (kv_len.to(torch.long) - 1).clamp_(0, S - 1)
             kc.index_copy_(1, pos, k_new)
             vc.index_copy_(1, pos, v_new)
+        if Hkv != H:  # (a copy: this path is for correctness, not speed)
+            kc, vc = (t[:, :, :, None].expand(B, S, Hkv, H // Hkv, D).reshape(B, S, H, D) for t in (kc, vc))
         return attention(q, kc, vc, scale, kv_len=kv_len)
     if not vec_ok(q):
         q = q.contiguous()
@@ -1506,7 +1603,7 @@ def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None)
         return (t.stride(0), t.stride(2)) if t is not None else (0, 0)
 
     st = (c_int64 * 14)(*bh(q), *kc.stride()[:3], *vc.stride()[:3], *bh(k_new), *bh(v_new), *bh(o))
-    _lib.call("csk_attention_decode", _p(o), _p(q), _p(kc), _p(vc), _p(k_new), _p(v_new), st, B, H, S, D,
-              float(scale), _p(kv_len), _p(ws), _p(cnt), _s())
+    _lib.call("csk_attention_decode_ex", _p(o), _p(q), _p(kc), _p(vc), _p(k_new), _p(v_new), st, B, H, Hkv, S, D,
+              float(scale), _p(kv_len), _p(ws), _p(cnt), _p(cos), _p(sin), 0 if cos is None else cos.shape[0], _s())
     DECODE_STATS["decode_attention"] += 1
     return o

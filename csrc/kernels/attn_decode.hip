@@ -1,7 +1,8 @@
 // Single-query split-KV attention for KV-cached decode, with the new token's
-// K/V append fused in.
+// K/V append, grouped K/V heads and the rotary embedding fused in.
 //
-//   o[b, 0, h, :] = softmax(q[b, 0, h, :] . K[b, :n, h, :]^T * scale) V[b, :n, h, :],  n = clamp(*kv_len, 0, S)
+//   o[b, 0, h, :] = softmax(q[b, 0, h, :] . K[b, :n, g, :]^T * scale) V[b, :n, g, :],  n = clamp(*kv_len, 0, S),
+//   g = h / (H / Hkv): H / Hkv consecutive query heads share one K/V head.
 //
 // One query row per (b, h) fills 1 of 16 rows of an MFMA tile and leaves one
 // workgroup per head walking up to S keys serially.  Here the grid is
@@ -21,8 +22,19 @@
 // n publishes (0, -inf, 0).
 //
 // Append: with k_new / v_new given, the lanes that own key n - 1 take it from
-// them instead of the cache and store it into the cache at that index.  No other
-// workgroup reads or writes that row in this launch.
+// them, never from the cache.  With H > Hkv the H / Hkv workgroups of a group
+// all own that index in the same split: every one of them reads k_new / v_new,
+// and only the workgroup of the group's first query head (h % (H / Hkv) == 0)
+// stores the row into the cache.  So in one launch cache row n - 1 of a K/V head
+// has exactly one writer and no reader.
+//
+// RoPE (cos / sin given: fp32 [P][D / 2] tables, P >= S, row n - 1): rotate-half
+// form, y[j] = x[j] cos[j] - x[j + D/2] sin[j], y[j + D/2] = x[j + D/2] cos[j] +
+// x[j] sin[j].  The partner half of a lane's 8 elements is a second 16-byte load.
+// The query is rotated in fp32 in every workgroup and used unrounded.  The new
+// key is rotated in fp32 and rounded to bf16 once; that rounded value is both
+// scored and stored, so the cache holds post-RoPE keys and a later step sees
+// exactly what this step used.  v_new is not touched.
 #include "common.h"
 
 #define AD_SPLIT 64     // keys per workgroup
@@ -32,16 +44,28 @@ struct AdArgs {
   const bf16_t* q;
   bf16_t* kc;
   bf16_t* vc;
-  const bf16_t* kn;  // new key / value [B, 1, H, D] or null
+  const bf16_t* kn;  // new key / value [B, 1, Hkv, D] or null
   const bf16_t* vn;
+  const float* cos;  // RoPE tables [P][D / 2] or null
+  const float* sin;
   bf16_t* o;
   float* ws;         // [B * H][nsplit][D + 2] fp32 partials
   unsigned* cnt;     // [B * H] arrival counters, zero between launches
   const int* kv_len;
   int64_t qs[2], ks[3], vs[3], kns[2], vns[2], os[2];  // element strides: (b, h) / (b, s, h)
   int B, H, S, nsplit;
+  int rep;           // H / Hkv query heads per K/V head
   float scale;
 };
+
+// x: this lane's 8 elements (chunk sub of a D-element row), xp: the same elements of the other half
+// (chunk sub ^ (LPK / 2)); cs / sn: cos / sin at (sub % (LPK / 2)) * 8 of the position's table row
+template <int LPK>
+__device__ __forceinline__ void ad_rope8(float* x, const float* xp, const float* cs, const float* sn, int sub) {
+  const float sg = sub < LPK / 2 ? -1.f : 1.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = __builtin_fmaf(sg * xp[j], sn[j], x[j] * cs[j]);
+}
 
 template <int D>
 __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a) {
@@ -64,8 +88,24 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
   const int sub = tid % LPK, slot = tid / LPK;
   const float ninf = -__builtin_inff();
 
-  float qf[8];
+  const int hk = h / a.rep;                    // the K/V head of this query head
+  const bool writer = h - hk * a.rep == 0;     // the one workgroup of the group that stores the appended row
+  const int psub = sub ^ (LPK / 2);            // the chunk that holds the rotation partners
+
+  float qf[8], cs[8], sn[8];
   unpack8(*(const uint4*)(a.q + b * a.qs[0] + h * a.qs[1] + sub * 8), qf);
+  if (a.cos != nullptr) {
+    const int pos = max(n - 1, 0);
+    CSK_DCHECK(pos >= 0 && pos < a.S, 3, pos, a.S);
+    const int64_t t = (int64_t)pos * (D / 2) + (sub % (LPK / 2)) * 8;
+    const float4 c0 = *(const float4*)(a.cos + t), c1 = *(const float4*)(a.cos + t + 4);
+    const float4 s0 = *(const float4*)(a.sin + t), s1 = *(const float4*)(a.sin + t + 4);
+    cs[0] = c0.x; cs[1] = c0.y; cs[2] = c0.z; cs[3] = c0.w; cs[4] = c1.x; cs[5] = c1.y; cs[6] = c1.z; cs[7] = c1.w;
+    sn[0] = s0.x; sn[1] = s0.y; sn[2] = s0.z; sn[3] = s0.w; sn[4] = s1.x; sn[5] = s1.y; sn[6] = s1.z; sn[7] = s1.w;
+    float qp[8];
+    unpack8(*(const uint4*)(a.q + b * a.qs[0] + h * a.qs[1] + psub * 8), qp);
+    ad_rope8<LPK>(qf, qp, cs, sn, sub);
+  }
 
   uint4 kr[NP], vr[NP];
 #pragma unroll
@@ -74,13 +114,23 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
     kr[p] = vr[p] = make_uint4(0u, 0u, 0u, 0u);
     if (idx < n) {
       CSK_DCHECK(idx >= 0 && idx < a.S, 1, idx, a.S);
-      bf16_t* kp = a.kc + b * a.ks[0] + (int64_t)idx * a.ks[1] + h * a.ks[2] + sub * 8;
-      bf16_t* vp = a.vc + b * a.vs[0] + (int64_t)idx * a.vs[1] + h * a.vs[2] + sub * 8;
+      bf16_t* kp = a.kc + b * a.ks[0] + (int64_t)idx * a.ks[1] + hk * a.ks[2] + sub * 8;
+      bf16_t* vp = a.vc + b * a.vs[0] + (int64_t)idx * a.vs[1] + hk * a.vs[2] + sub * 8;
       if (a.kn != nullptr && idx == n - 1) {
-        kr[p] = *(const uint4*)(a.kn + b * a.kns[0] + h * a.kns[1] + sub * 8);
-        vr[p] = *(const uint4*)(a.vn + b * a.vns[0] + h * a.vns[1] + sub * 8);
-        *(uint4*)kp = kr[p];
-        *(uint4*)vp = vr[p];
+        const bf16_t* kn = a.kn + b * a.kns[0] + hk * a.kns[1];
+        kr[p] = *(const uint4*)(kn + sub * 8);
+        vr[p] = *(const uint4*)(a.vn + b * a.vns[0] + hk * a.vns[1] + sub * 8);
+        if (a.cos != nullptr) {
+          float kf[8], kq[8];
+          unpack8(kr[p], kf);
+          unpack8(*(const uint4*)(kn + psub * 8), kq);
+          ad_rope8<LPK>(kf, kq, cs, sn, sub);
+          kr[p] = pack8(kf);  // the one rounding: scored below and stored here
+        }
+        if (writer) {
+          *(uint4*)kp = kr[p];
+          *(uint4*)vp = vr[p];
+        }
       } else {
         kr[p] = *(const uint4*)kp;
         vr[p] = *(const uint4*)vp;
@@ -206,9 +256,15 @@ static bool ad_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // st: element strides q (b, h), k (b, s, h), v (b, s, h), k_new (b, h), v_new (b, h), o (b, h).
 // ws: fp32 [B * H * ceil(S / AD_SPLIT) * (D + 2)]; cnt: uint32 [B * H], zero on entry, zero on exit.
 // Graph-capturable: no allocation, no sync.
-CSK_API int csk_attention_decode(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
-                                 const int64_t* st, int B, int H, int S, int D, float scale, const void* kv_len,
-                                 void* ws, void* cnt, hipStream_t stream) {
+// Hkv: K/V heads of the caches and of k_new / v_new (H % Hkv == 0; their head strides in st are per K/V head).
+// cos / sin: fp32 [P][D / 2] RoPE tables, P >= S, 16-byte aligned, or both null.
+CSK_API int csk_attention_decode_ex(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
+                                    const int64_t* st, int B, int H, int Hkv, int S, int D, float scale,
+                                    const void* kv_len, void* ws, void* cnt, const void* cos, const void* sin, int P,
+                                    hipStream_t stream) {
+  if (Hkv < 1 || H % Hkv != 0 || (cos == nullptr) != (sin == nullptr) || (cos != nullptr && P < S) ||
+      !ad_aligned16(cos) || !ad_aligned16(sin))
+    return (int)hipErrorInvalidValue;
   if (o == nullptr || q == nullptr || kc == nullptr || vc == nullptr || st == nullptr || kv_len == nullptr ||
       ws == nullptr || cnt == nullptr || (kn == nullptr) != (vn == nullptr))
     return (int)hipErrorInvalidValue;
@@ -226,12 +282,20 @@ CSK_API int csk_attention_decode(void* o, const void* q, void* kc, void* vc, con
   a.vs[0] = st[5]; a.vs[1] = st[6]; a.vs[2] = st[7];
   a.kns[0] = st[8]; a.kns[1] = st[9]; a.vns[0] = st[10]; a.vns[1] = st[11];
   a.os[0] = st[12]; a.os[1] = st[13];
+  a.cos = (const float*)cos; a.sin = (const float*)sin; a.rep = H / Hkv;
   a.B = B; a.H = H; a.S = S; a.nsplit = (S + AD_SPLIT - 1) / AD_SPLIT; a.scale = scale;
   const dim3 grid(a.nsplit, B * H);
   if (D == 32) hipLaunchKernelGGL(attn_decode_kernel<32>, grid, dim3(AD_THREADS), 0, stream, a);
   else if (D == 64) hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(AD_THREADS), 0, stream, a);
   else hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(AD_THREADS), 0, stream, a);
   CSK_CHECK_LAUNCH();
+}
+
+CSK_API int csk_attention_decode(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
+                                 const int64_t* st, int B, int H, int S, int D, float scale, const void* kv_len,
+                                 void* ws, void* cnt, hipStream_t stream) {
+  return csk_attention_decode_ex(o, q, kc, vc, kn, vn, st, B, H, H, S, D, scale, kv_len, ws, cnt, nullptr, nullptr, 0,
+                                 stream);
 }
 
 CSK_DEBUG_EXPORT(attn_decode)
