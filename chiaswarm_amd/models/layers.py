@@ -199,8 +199,10 @@ class Attention(Prepared):
             return self.attend_q(self.to_q(x), kv, ctx if ctx is not None else x, residual)
         return self.attend_qkv(ops.gemm(x, self.w_qkv, self.b_qkv), residual, causal=causal)
 
-    def attend_qkv(self, qkv, residual=None, causal=False, row_stats=False):
-        """Self-attention from the fused QKV projection [B, S, 3*H*D]."""
+    def attend_qkv(self, qkv, residual=None, causal=False, row_stats=False, project=True):
+        """Self-attention from the fused QKV projection [B, S, 3*H*D].
+        ``project=False``: the attention output [B, S, H*D] itself, for a
+        consumer that runs the out-projection (the fused cross-attention block)."""
         b, s, _ = qkv.shape
         h, d = self.heads, self.dim_head
         qkv = qkv.view(b, s, 3, h, d)
@@ -209,6 +211,8 @@ class Attention(Prepared):
             q, k = qkv[:, :, 0].float().transpose(1, 2), qkv[:, :, 1].float().transpose(1, 2)
             store.append(torch.softmax(q @ k.transpose(-1, -2) * self.scale, dim=-1))
         o = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], self.scale, causal=causal)
+        if not project:
+            return o.reshape(b, s, h * d)
         return self.to_out[0](o.reshape(b, s, h * d), residual=residual, row_stats=row_stats)
 
     def attend_q(self, q, kv, ctx, residual=None, row_stats=False):
@@ -310,9 +314,14 @@ class BasicTransformerBlock(nn.Module):
             folds[name] = f
         return f[1]
 
-    def forward(self, x, ctx=None, kv=None, row_stats=None, dup=False, qkv=None):
+    def forward(self, x, ctx=None, kv=None, row_stats=None, dup=False, qkv=None, tail=None):
         """``qkv``: this block's self-attention projection LN1(x) Wqkv^T already
         computed (the fused transformer-input kernel, Transformer2D.forward).
+        ``tail = (wpp, bp, xin, gn_rows)``: the transformer's proj_out (packed,
+        ``ops.pack_ff_proj``), its residual and the rows per sample of the
+        GroupNorm statistics; where the fused feed-forward takes it
+        (``ops.ff_proj_fusable``) the block returns ``(z, True)``, z = xin +
+        proj_out(block output) shaped like ``xin``, else ``(block output, False)``.
 
         On the HIP path every LayerNorm runs inside the GEMM that consumes it
         (``ops.layer_norm_gemm``): each producer GEMM (proj_in, the attention
@@ -332,6 +341,22 @@ class BasicTransformerBlock(nn.Module):
             fus = ops.ln_fusable(x)
             qkv = ops.layer_norm_gemm(x, self.norm1, a1.w_qkv, a1.b_qkv,
                                       self._fold("qkv", a1.w_qkv, a1.b_qkv, self.norm1) if fus else None)
+        if hip and kv is not None and x.dim() == 3 and ops.xattn_pre_fusable(x, kv, x.shape[1], dup):
+            # the fused cross-attention kernel below (csrc/kernels/xattn.hip) with the
+            # self-attention out-projection + residual as its prologue: its input never
+            # reaches HBM; with ``dup`` one launch serves both CFG halves straight from
+            # the half-batch attention output
+            f = self._fold("q", a2.to_q.weight, a2.to_q.bias, self.norm2)
+            hit = self.__dict__.get("_q_perm")
+            if hit is None or hit[0] is not f:
+                hit = (f, ops.permute_xattn_q(f[0]))
+                self.__dict__["_q_perm"] = hit
+            o = a1.attend_qkv(qkv, project=False)
+            x = ops.xattn_block(None, hit[1], f[1], f[2], kv, a2.to_out[0].weight, a2.to_out[0].bias, self.norm2.eps,
+                                a2.scale, x.shape[1], row_stats=hip,
+                                pre=(o, x, a1.to_out[0].weight, a1.to_out[0].bias),
+                                batch=(2 if dup else 1) * x.shape[0])
+            return self._ff_tail(x, row_stats, hip, tail)
         x = a1.attend_qkv(qkv, residual=x, row_stats=hip)
         if hip and not dup and kv is not None and x.dim() == 3 and ops.xattn_fusable(x, kv, x.shape[1]):
             # LN2 + Q projection + attention over the context + out-projection +
@@ -355,19 +380,33 @@ class BasicTransformerBlock(nn.Module):
             if dup:
                 q, x = ops.dup2(q), ops.dup2(x)
             x = a2.attend_q(q, kv, ctx if ctx is not None else x, residual=x, row_stats=hip)
+        return self._ff_tail(x, row_stats, hip, tail)
+
+    def _ff_tail(self, x, row_stats, hip, tail):
+        """The feed-forward sub-block (and ``tail``, see ``forward``)."""
+        ff = self.ff
         if hip and not row_stats and ops.ff_fusable(x, ff.inner):
             # LN3 + GEGLU + down-projection + residual in ONE kernel
             # (csrc/kernels/ff.hip): the [M, 4C] intermediate never reaches HBM
             w1p, b1p, w2p = ff.fused_weights()
+            seg = ops.ff_proj_fusable(x, ff.inner, tail[3]) if tail is not None and w1p is not None else 0
+            if seg:
+                # ... and the transformer's proj_out + residual + GroupNorm
+                # statistics in the same kernel: the FF output stays on chip too
+                wpp, bp, xin, gn_rows = tail
+                return ops.ff_fused_proj(x, self.norm3.weight, self.norm3.bias, w1p, b1p, w2p, ff.net[2].bias, wpp, bp,
+                                         xin, self.norm3.eps, gn_rows, seg), True
             if w1p is not None:
-                return ops.ff_fused(x, self.norm3.weight, self.norm3.bias, w1p, b1p, w2p, ff.net[2].bias,
-                                    self.norm3.eps)
+                y = ops.ff_fused(x, self.norm3.weight, self.norm3.bias, w1p, b1p, w2p, ff.net[2].bias,
+                                 self.norm3.eps)
+                return y if tail is None else (y, False)
         g = ff.net[0]
         g.ensure()
         fus = ops.ln_fusable(x)
         hdn = ops.layer_norm_gemm(x, self.norm3, g.wp, g.bp, self._fold("ff", g.wp, g.bp, self.norm3) if fus else None,
                                   act="geglu")
-        return ff.net[2](hdn, residual=x, row_stats=row_stats)
+        y = ff.net[2](hdn, residual=x, row_stats=row_stats)
+        return y if tail is None else (y, False)
 
 
 class Transformer2D(nn.Module):
@@ -409,6 +448,25 @@ class Transformer2D(nn.Module):
             self.__dict__["_xin"] = hit
         return hit[1]
 
+    def _proj_tail(self, x):
+        """proj_out packed for the tail of the last block's fused feed-forward
+        (csrc/kernels/ff.hip, PROJ variant), or None where it cannot ride there:
+        a C x C ``Linear`` at C = 320 and a contiguous bf16 residual.  Repacked
+        when the weight changes (e.g. a LoRA merge)."""
+        po = self.proj_out
+        c = x.shape[-1]
+        if (not isinstance(po, Linear) or not self.transformer_blocks or c != 320 or tuple(po.weight.shape) != (c, c)
+                or x.dtype != torch.bfloat16 or po.weight.dtype != torch.bfloat16 or not x.is_contiguous()
+                or not ops.row_stats_wanted(x)):
+            return None
+        w = po.weight
+        key = (w.data_ptr(), w._version, w.device, w.dtype)
+        hit = self.__dict__.get("_ffproj")
+        if hit is None or hit[0] != key:
+            hit = (key, ops.pack_ff_proj(w.detach()))
+            self.__dict__["_ffproj"] = hit
+        return hit[1]
+
     def _xin_ok(self, x) -> bool:
         if not ops.row_stats_wanted(x) or not self.transformer_blocks:
             return False
@@ -440,14 +498,18 @@ class Transformer2D(nn.Module):
             if rows is not None:
                 h._csk_rows = rows
         nb = len(self.transformer_blocks)
+        wpp = self._proj_tail(x)  # proj_out rides in the last block's fused feed-forward where it can
         for i, blk in enumerate(self.transformer_blocks):
-            if dup and i == 0:
-                h = blk(h, ctx=ctx, kv=None if kvs is None else kvs[i], row_stats=hip and i + 1 < nb, dup=True,
-                        qkv=qkv0)
+            d = dup and i == 0
+            if d:
                 x, b = ops.dup2(x), 2 * b
-                continue
-            h = blk(h, ctx=ctx, kv=None if kvs is None else kvs[i], row_stats=hip and i + 1 < nb,
-                    qkv=qkv0 if i == 0 else None)
+            tail = (wpp, self.proj_out.bias, x, hh * ww) if wpp is not None and i + 1 == nb else None
+            h = blk(h, ctx=ctx, kv=None if kvs is None else kvs[i], row_stats=hip and i + 1 < nb, dup=d,
+                    qkv=qkv0 if i == 0 else None, tail=tail)
+            if tail is not None:
+                h, done = h
+                if done:
+                    return h
         if isinstance(self.proj_out, Linear):
             return ops.gemm(h.view(b, hh, ww, c), self.proj_out.weight, self.proj_out.bias, residual=x,
                             gn_rows=hh * ww)

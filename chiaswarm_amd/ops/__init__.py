@@ -283,28 +283,41 @@ def pack_ff_fused(w1, b1, w2):
     b1p = None
     if b1 is not None:
         b1p = torch.stack((b1[:inner].reshape(t, 16), b1[inner:].reshape(t, 16)), 1).reshape(t, 32).float()
+    return w1p.contiguous(), (None if b1p is None else b1p.contiguous()), _pack_ff_w2(w2)
+
+
+def _pack_ff_w2(w2):
+    """[C, K] -> [K/32, C/32, 32, 32]: per 32 input columns one swizzled [32][32]
+    image per 32 output rows, columns in 16-blocks ordered ``_FF_PERM``."""
+    c, inner = w2.shape
+    _, k4 = _ff_keys(w2.device)
     perm = torch.tensor(_FF_PERM, device=w2.device)
-    w2q = w2.reshape(c, t, 16).index_select(2, perm).reshape(c // 32, 32, inner // 32, 4, 8)
+    w2q = w2.reshape(c, inner // 16, 16).index_select(2, perm).reshape(c // 32, 32, inner // 32, 4, 8)
     w2p = torch.gather(w2q, 3, k4[None, :, None, :, None].expand(c // 32, 32, inner // 32, 4, 8))
-    w2p = w2p.permute(2, 0, 1, 3, 4).reshape(inner // 32, c // 32, 32, 32)
-    return w1p.contiguous(), (None if b1p is None else b1p.contiguous()), w2p.contiguous()
+    return w2p.permute(2, 0, 1, 3, 4).reshape(inner // 32, c // 32, 32, 32).contiguous()
+
+
+def _unpack_ff_w2(w2p):
+    nc, no = w2p.shape[0], w2p.shape[1]
+    c, inner = 32 * no, 32 * nc
+    _, k4 = _ff_keys(w2p.device)
+    inv4 = torch.argsort(k4, 1)
+    y = w2p.reshape(nc, no, 32, 4, 8).permute(1, 2, 0, 3, 4)  # [o, r, c, pos, e]
+    y = torch.gather(y, 3, inv4[None, :, None, :, None].expand(no, 32, nc, 4, 8)).reshape(c, inner // 16, 16)
+    return y[:, :, torch.argsort(torch.tensor(_FF_PERM, device=w2p.device))].reshape(c, inner)
 
 
 def unpack_ff_fused(w1p, b1p, w2p):
     """Inverse of ``pack_ff_fused``: (w1 [2I, C], b1 [2I] or None, w2 [C, I])."""
     t, si = w1p.shape[0], w1p.shape[1]
     c, inner = 64 * si, 16 * t
-    k8, k4 = _ff_keys(w1p.device)
-    inv8, inv4 = torch.argsort(k8, 1), torch.argsort(k4, 1)
+    k8, _ = _ff_keys(w1p.device)
+    inv8 = torch.argsort(k8, 1)
     x = w1p.reshape(t, si, 32, 8, 8).permute(0, 2, 1, 3, 4)  # [t, r, si, pos, e]
     x = torch.gather(x, 3, inv8[None, :, None, :, None].expand(t, 32, si, 8, 8)).reshape(t, 32, c)
     w1 = torch.cat((x[:, :16].reshape(inner, c), x[:, 16:].reshape(inner, c)), 0)
     b1 = None if b1p is None else torch.cat((b1p[:, :16].reshape(inner), b1p[:, 16:].reshape(inner)), 0)
-    nc, no = w2p.shape[0], w2p.shape[1]
-    y = w2p.reshape(nc, no, 32, 4, 8).permute(1, 2, 0, 3, 4)  # [o, r, c, pos, e]
-    y = torch.gather(y, 3, inv4[None, :, None, :, None].expand(no, 32, nc, 4, 8)).reshape(c, inner // 16, 16)
-    w2 = y[:, :, torch.argsort(torch.tensor(_FF_PERM, device=w2p.device))].reshape(c, inner)
-    return w1, b1, w2
+    return w1, b1, _unpack_ff_w2(w2p)
 
 
 def ff_fusable(x: torch.Tensor, inner: int) -> bool:
@@ -337,6 +350,50 @@ def _ref_ff_fused(x, gamma, beta, w1p, b1p, w2p, b2, eps):
     hid = vg[..., :inner] * torch.nn.functional.gelu(vg[..., inner:])
     y = torch.nn.functional.linear(hid, w2.float(), None if b2 is None else b2.float())
     return (xf + y).to(x.dtype)
+
+
+def pack_ff_proj(wp):
+    """The transformer's ``proj_out`` weight [C, C] for the tail of the fused
+    feed-forward (ff.hip, PROJ variant): packed exactly like its W2, the FF
+    output's channels taking the place of the intermediates: [C/32, C/32, 32, 32]."""
+    c = wp.shape[0]
+    return _pack_ff_w2(wp.reshape(c, c))
+
+
+def unpack_ff_proj(wpp):
+    """Inverse of ``pack_ff_proj``: [C, C]."""
+    return _unpack_ff_w2(wpp)
+
+
+def ff_proj_fusable(x: torch.Tensor, inner: int, gn_rows: int) -> int:
+    """GroupNorm segment height (non-zero) when the fused feed-forward also
+    takes the transformer's proj_out for this block (HIP path, C = 320, whole
+    128-row tiles), else 0."""
+    if not use_hip(x) or x.dim() != 3:
+        return 0
+    from . import hip_ops
+
+    return hip_ops.ff_proj_ok(x, inner, gn_rows)
+
+
+def ff_fused_proj(x, gamma, beta, w1p, b1p, w2p, b2, wpp, bp, xin, eps, gn_rows=0, seg=0):
+    """xin + proj_out(x + FF(LayerNorm(x))), shaped like ``xin``: one HIP kernel
+    (with the GroupNorm partials of the result when ``seg`` > 0), or the fp32
+    reference composition of the packed weights."""
+    if use_hip(x):
+        from . import hip_ops
+
+        return hip_ops.ff_geglu_proj(x, gamma, beta, w1p, b1p, w2p, b2, wpp, bp, xin, eps, gn_rows, seg)
+    return _ref_ff_fused_proj(x, gamma, beta, w1p, b1p, w2p, b2, wpp, bp, xin, eps)
+
+
+def _ref_ff_fused_proj(x, gamma, beta, w1p, b1p, w2p, b2, wpp, bp, xin, eps):
+    """fp32 reference from the packed weights: ``_ref_ff_fused`` (kept in fp32),
+    then the projection, its bias and the residual ``xin``."""
+    wp = unpack_ff_proj(wpp)
+    y = _ref_ff_fused(x.float(), gamma, beta, w1p, b1p, w2p, b2, eps)
+    z = torch.nn.functional.linear(y, wp.float(), None if bp is None else bp.float())
+    return (xin.float() + z.reshape(xin.shape)).to(x.dtype)
 
 
 def _a_tiles(w):
@@ -436,20 +493,68 @@ def xattn_fusable(x: torch.Tensor, kv, rows_per_b: int) -> bool:
     return hip_ops.xattn_ok(x, kv, rows_per_b)
 
 
-def xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=True):
+# column order of the folded query weight for the fused block's prologue
+# variant (csrc/kernels/xattn.hip PRE): within each 32-column block, position
+# 8 g + j holds column 4 g + j (j < 4) or 16 + 4 g + j - 4 (the k-slot order in
+# which the prologue's accumulators arrive)
+_XQ_PERM = tuple((4 * g + j if j < 4 else 16 + 4 * g + j - 4) for g in range(4) for j in range(8))
+
+
+def permute_xattn_q(wq):
+    """Folded query weight [N, C] (C % 32 == 0) with its columns in the
+    prologue variant's order; ``colsum`` and the bias are unaffected."""
+    n, c = wq.shape
+    return wq.reshape(n, c // 32, 32)[:, :, torch.tensor(_XQ_PERM, device=wq.device)].reshape(n, c).contiguous()
+
+
+def unpermute_xattn_q(wqp):
+    """Inverse of ``permute_xattn_q``."""
+    n, c = wqp.shape
+    inv = torch.argsort(torch.tensor(_XQ_PERM, device=wqp.device))
+    return wqp.reshape(n, c // 32, 32)[:, :, inv].reshape(n, c).contiguous()
+
+
+def xattn_pre_fusable(o: torch.Tensor, kv, rows_per_b: int, dup=False) -> bool:
+    """The fused cross-attention sub-block also takes the preceding
+    out-projection of the attention output ``o`` as its prologue (``dup``: for
+    both CFG halves from the one half in ``o``)."""
+    if not use_hip(o):
+        return False
+    from . import hip_ops
+
+    return hip_ops.xattn_pre_ok(o, kv, rows_per_b, dup)
+
+
+def xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=True, pre=None, batch=None):
     """x + CrossAttention(LayerNorm(x)) with the LayerNorm folded into ``wq`` /
     ``colsum`` / ``bq`` (fold_layer_norm) and ``kv`` the per-request K/V
-    [B, Skv, 2, H, D]; one HIP kernel, or the reference composition."""
-    if use_hip(x):
+    [B, Skv, 2, H, D]; one HIP kernel, or the reference composition.
+    ``pre = (o, h0, wo1, bo1)`` with ``x`` None: x = h0 + o wo1^T + bo1, the
+    out-projection of the preceding attention, is formed inside (``wq`` then
+    ``permute_xattn_q``'d), for ``batch`` samples (a multiple of ``o``'s, which
+    then repeats)."""
+    if use_hip(x if pre is None else pre[0]):
         from . import hip_ops
 
-        return hip_ops.xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=row_stats)
-    return _ref_xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale)
+        return hip_ops.xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=row_stats,
+                                   pre=pre, batch=batch)
+    return _ref_xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, pre=pre, batch=batch)
 
 
-def _ref_xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale):
+def _ref_xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, pre=None, batch=None):
     """fp32 reference: LN(x) @ Wq^T from the folded form (== the unfolded LN +
-    projection), softmax attention over kv, out-projection, residual."""
+    projection), softmax attention over kv, out-projection, residual.  With
+    ``pre``: x from the out-projection (fp32), ``wq`` un-permuted."""
+    if pre is not None:
+        o, h0, wo1, bo1 = pre
+        xf = h0.float() + o.float() @ wo1.float().t()
+        if bo1 is not None:
+            xf = xf + bo1.float()
+        if batch is not None and batch != o.shape[0]:
+            xf = xf.repeat(batch // o.shape[0], 1, 1)
+        dt, x, wq = o.dtype, xf, unpermute_xattn_q(wq)
+    else:
+        dt = x.dtype
     xf = x.float()
     mean = xf.mean(-1, keepdim=True)
     rstd = torch.rsqrt(xf.var(-1, unbiased=False, keepdim=True) + eps)
@@ -463,7 +568,7 @@ def _ref_xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale):
     y = o @ wo.float().t() + xf
     if bo is not None:
         y = y + bo.float()
-    return y.to(x.dtype)
+    return y.to(dt)
 
 
 def cat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -1202,20 +1202,86 @@ def xattn_ok(x, kv, rows_per_b) -> bool:
     of 64), <= 80 context tokens, whole 128-row tiles of one sample, and a grid
     of at least XATTN_MIN_WG workgroups."""
     C = x.shape[-1]
-    if x.numel() // max(C, 1) // 128 < XATTN_MIN_WG:
+    return _xattn_rows_ok(x.numel() // max(C, 1), C, kv, rows_per_b)
+
+
+def _xattn_rows_ok(M, C, kv, rows_per_b) -> bool:
+    if M // 128 < XATTN_MIN_WG:
         return False
     return (XATTN_FUSED and C in XATTN_CHANNELS and kv is not None and kv.dim() == 5 and kv.shape[2] == 2
             and kv.shape[3] * kv.shape[4] == C and kv.shape[4] == 64 and 1 <= kv.shape[1] <= 80
-            and rows_per_b % 128 == 0 and x.numel() // C % rows_per_b == 0
-            and kv.shape[0] >= x.numel() // C // rows_per_b)
+            and rows_per_b % 128 == 0 and M % rows_per_b == 0
+            and kv.shape[0] >= M // rows_per_b)
 
 
-def xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=True):
+# The self-attention out-projection as the prologue of the fused block
+# (xattn.hip, PRE variant): x = bf16(h0 + O Wo1^T + bo1) is formed in registers
+# and never stored.  CSK_XATTN_PRE=0: the out-projection stays its own GEMM.
+# CSK_XATTN_DUP=0: the CFG-shared first block (both halves from the half-batch
+# self-attention, source row m % src_rows) keeps the unfused chain.
+# (tools/abstep.py arms xpre0 / xpre1, xdup0 / xdup1)
+sig("csk_xattn_block_pre_ok", c_int, c_int, c_int, c_int, c_int, c_int)
+sig("csk_xattn_block_pre", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+    c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p)
+XATTN_PRE = os.environ.get("CSK_XATTN_PRE", "1") == "1"
+XATTN_DUP = os.environ.get("CSK_XATTN_DUP", "1") == "1"
+XATTN_PRE_STATS = [0]  # calls with the prologue, same batch (tests assert the fused path ran)
+XATTN_DUP_STATS = [0]  # calls with the prologue that also double the batch
+
+
+def xattn_pre_ok(o, kv, rows_per_b, dup=False) -> bool:
+    """``xattn_ok`` for the block whose input the prologue forms from the
+    attention output ``o`` [b, S, C] (``dup``: for twice the batch)."""
+    if not XATTN_PRE or (dup and not XATTN_DUP) or o.dim() != 3 or o.dtype != torch.bfloat16:
+        return False
+    b, s, c = o.shape
+    return _xattn_rows_ok((2 * b if dup else b) * s, c, kv, rows_per_b)
+
+
+def _xattn_block_pre(pre, batch, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats):
+    o, h0, wo1, bo1 = pre
+    for t, n in ((o, "o"), (h0, "h0"), (wo1, "wo1"), (wq, "wq"), (bq, "bq"), (kv, "kv"), (wo, "wo")):
+        _bf16(t, "xattn_block.pre." + n)
+    for t, n in ((bo1, "bo1"), (bo, "bo")):
+        if t is not None:
+            _bf16(t, "xattn_block.pre." + n)
+    b, s, C = o.shape
+    batch = b if batch is None else int(batch)
+    if h0.shape != o.shape or tuple(wo1.shape) != (C, C) or batch % b:
+        raise ValueError(f"xattn_block: prologue operands {tuple(o.shape)} / {tuple(h0.shape)} / {tuple(wo1.shape)} "
+                         f"do not match batch {batch}")
+    src_rows, M = b * s, batch * s
+    kv = kv.contiguous()
+    if colsum.dtype != torch.float32 or colsum.numel() != C:
+        raise ValueError("xattn_block: colsum must be fp32 [C]")
+    if _lib.call_int("csk_xattn_block_pre_ok", M, C, int(rows_per_b), int(kv.shape[0]), int(kv.shape[1]),
+                     src_rows) != 1:
+        raise ValueError(f"xattn_block: unsupported prologue shape M={M} C={C} rows/sample={rows_per_b} "
+                         f"kv={tuple(kv.shape)} source rows={src_rows}")
+    y = torch.empty((batch, s, C), dtype=torch.bfloat16, device=o.device)
+    rp = torch.empty(M * 2, dtype=torch.float32, device=o.device) if row_stats else None
+    (XATTN_DUP_STATS if batch != b else XATTN_PRE_STATS)[0] += 1
+    _lib.call("csk_xattn_block_pre", _p(y), _p(o.contiguous()), _p(h0.contiguous()), _p(wo1.contiguous()),
+              _p(None if bo1 is None else bo1.contiguous()), _p(wq.contiguous()), _p(colsum.contiguous()),
+              _p(bq.contiguous()), _p(kv), _p(wo.contiguous()), _p(None if bo is None else bo.contiguous()), _p(rp),
+              M, C, int(rows_per_b), int(kv.shape[0]), int(kv.shape[1]), src_rows, float(eps), float(scale), _s())
+    if rp is not None:
+        y._csk_rows = (rp, 1, C)
+    return y
+
+
+def xattn_block(x, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats=True, pre=None, batch=None):
     """y = x + softmax((LN(x) Wq^T) scale K^T) V Wo^T + bo in ONE kernel
     (LayerNorm folded into ``wq`` / ``colsum`` / ``bq``: ops.fold_layer_norm).
     x: [B, S, C] bf16; kv: [Bc, Skv, 2, H, 64] (Attention.context_kv).  With
     ``row_stats`` the output carries ``_csk_rows`` = (part, 1, C) for the next
-    fused LayerNorm."""
+    fused LayerNorm.
+    ``pre = (o, h0, wo1, bo1)`` (then ``x`` is None): x = h0 + o wo1^T + bo1 is
+    formed in the kernel's prologue — ``wq`` must then be column-permuted by
+    ``ops.permute_xattn_q`` — for ``batch`` samples (default: those of ``o``; a
+    multiple repeats ``o`` / ``h0``, the K/V differ)."""
+    if pre is not None:
+        return _xattn_block_pre(pre, batch, wq, colsum, bq, kv, wo, bo, eps, scale, rows_per_b, row_stats)
     for t, n in ((x, "x"), (wq, "wq"), (bq, "bq"), (kv, "kv"), (wo, "wo")):
         _bf16(t, "xattn_block." + n)
     if bo is not None:
@@ -1285,6 +1351,83 @@ def ff_geglu(x, gamma, beta, w1p, b1p, w2p, b2, eps):
               _p(w1p.contiguous()), _p(None if b1p is None else b1p.contiguous()), _p(w2p.contiguous()),
               _p(None if b2 is None else b2.contiguous()), M, C, inner, float(eps), _s())
     return y.view(x.shape)
+
+
+# The transformer's proj_out in the tail of the fused feed-forward
+# (ff.hip, PROJ variant): z = x_in + Wp bf16(ff(x)) + bp and the GroupNorm
+# partials of z in the same kernel; the FF output never reaches HBM.
+# CSK_FF_PROJ=0: proj_out stays its own GEMM (tools/abstep.py arms ffp0 / ffp1).
+sig("csk_ff_geglu_proj_ok", c_int, c_int, c_int, c_int, c_int)
+sig("csk_ff_geglu_proj", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+    c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p)
+FF_PROJ = os.environ.get("CSK_FF_PROJ", "1") == "1"
+FF_PROJ_STATS = [0]  # calls (tests assert the fused path ran)
+
+
+def ff_proj_seg(M, C, gn_rows) -> int:
+    """GroupNorm-statistics segment height the stand-alone proj_out GEMM
+    [M, C] x [C, C] writes for this shape (``gemm``'s tile plan, ``_gn_seg``):
+    the fused kernel emits the same one, so every consumer — ``group_norm_cat``
+    wants equal segments of both operands — keeps the path it has."""
+    hit = tuning._lookup(tuning.table(), f"g:{M}:{C}:{C}:0")
+    tile, split = (int(hit[0]), int(hit[1])) if hit is not None else tuning.heuristic(M, C, C)
+    if split < 0 and tile not in tuning.GLDS:
+        split = 1
+    return _gn_seg(tile, split, gn_rows, M, 0, C)
+
+
+def ff_proj_ok(x, inner: int, gn_rows: int) -> int:
+    """Segment height (32 / 64 / 128) when the fused FF + proj_out kernel takes
+    this block, else 0."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    if not (FF_PROJ and ff_fused_ok(x, inner)):
+        return 0
+    seg = ff_proj_seg(M, C, gn_rows)
+    if seg not in (32, 64, 128) or _lib.call_int("csk_ff_geglu_proj_ok", M, C, inner, seg, gn_rows) != 1:
+        return 0
+    return seg
+
+
+def ff_geglu_proj(x, gamma, beta, w1p, b1p, w2p, b2, wpp, bp, xin, eps, gn_rows=0, seg=0):
+    """z = xin + Wp bf16(x + W2 GEGLU(W1 LayerNorm(x) + b1) + b2) + bp in ONE
+    kernel (C = 320, M a multiple of 128): ``ff_geglu`` with the C x C
+    projection ``wpp`` (``ops.pack_ff_proj``) in its tail.  ``seg`` (32, 64 or
+    128, dividing ``gn_rows`` = rows per sample): also the GroupNorm partials
+    of z per ``seg`` rows, attached as ``z._csk_gn`` like ``gemm(gn_rows=)``."""
+    for t, n in ((x, "x"), (gamma, "gamma"), (w1p, "w1p"), (w2p, "w2p"), (wpp, "wpp"), (xin, "xin")):
+        _bf16(t, "ff_geglu_proj." + n)
+    for t, n in ((beta, "beta"), (b2, "b2"), (bp, "bp")):
+        if t is not None:
+            _bf16(t, "ff_geglu_proj." + n)
+    if b1p is not None and b1p.dtype != torch.float32:
+        raise ValueError("ff_geglu_proj: b1p must be fp32")
+    C = x.shape[-1]
+    M = x.numel() // C
+    inner = 32 * w2p.shape[0]
+    if xin.numel() != M * C or tuple(wpp.shape) != (C // 32, C // 32, 32, 32):
+        raise ValueError(f"ff_geglu_proj: residual {tuple(xin.shape)} / packed proj {tuple(wpp.shape)} do not match "
+                         f"{tuple(x.shape)}")
+    if _lib.call_int("csk_ff_geglu_proj_ok", M, C, inner, int(seg), int(gn_rows)) != 1:
+        raise ValueError(f"ff_geglu_proj: unsupported shape M={M} C={C} I={inner} seg={seg} rows/sample={gn_rows}")
+    x2, r2 = x.reshape(M, C), xin.reshape(M, C)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if not r2.is_contiguous():
+        r2 = r2.contiguous()
+    z = torch.empty((M, C), dtype=torch.bfloat16, device=x.device)
+    part = _gn_part(M, C, seg, x.device) if seg else None
+    FF_PROJ_STATS[0] += 1
+    _lib.call("csk_ff_geglu_proj", _p(z), _p(x2), _p(gamma.contiguous()),
+              _p(None if beta is None else beta.contiguous()), _p(w1p.contiguous()),
+              _p(None if b1p is None else b1p.contiguous()), _p(w2p.contiguous()),
+              _p(None if b2 is None else b2.contiguous()), _p(wpp.contiguous()),
+              _p(None if bp is None else bp.contiguous()), _p(r2), _p(part), int(seg), int(gn_rows), M, C, inner,
+              float(eps), _s())
+    z = z.view(xin.shape)
+    if part is not None:
+        z._csk_gn = (part, seg)
+    return z
 
 
 sig("csk_set_xattn_probe", c_int)

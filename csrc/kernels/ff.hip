@@ -30,6 +30,22 @@
 // 320 x 32], each 20 MFMAs per wave; six slots stay in flight, one barrier per
 // slot frees the slot just consumed for the next DMA (counted vmcnt waits).
 // The MFMA floor is 32 us per 128 rows (2400 MFMAs x 32 cycles per wave).
+//
+// PROJ variant (csk_ff_geglu_proj): the transformer's proj_out rides in the
+// tail, so y never reaches HBM either:
+//
+//   z = x_in + Wp bf16(y) + bp        (+ the GroupNorm partials of z)
+//
+// out[o][8 s .. 8 s + 7] of a lane, + b2 + x and rounded to bf16 (the rounding
+// the stored y gets), IS the B fragment of the 16-channel k-step 32 o + 16 s in
+// the k-slot order of the GEGLU -> W2 hand-off, so Wp is packed like W2
+// (ops.pack_ff_proj) and streams through the same ring as C / 32 more slots
+// behind the last W2 slice (20 MFMAs per wave each, the w2_slice loop), into a
+// second set of 160 accumulators.  The ring is free afterwards: the rounded
+// 128 x C tile is staged in it, each wave stores its 32 rows as whole 640-byte
+// rows (16 B per lane) and takes the per-channel (mean, M2) of its slab in the
+// same pass; the slabs are Chan-merged in fixed order to the segment height
+// the host asks for (gemm_common.h gn_part layout).
 #include "common.h"
 
 #include "attn_tile.h"
@@ -48,9 +64,16 @@ struct FfArgs {
                         // 16-column block ordered 0-3, 8-11, 4-7, 12-15
   const bf16_t* b2;     // [C] (or null)
   bf16_t* y;            // [M][C]
+  // PROJ variant: y = xin + Wp bf16(ff) + bp
+  const bf16_t* wp;     // [C/32][C/32][32][32]: proj_out packed like w2 (ops.pack_ff_proj)
+  const bf16_t* bp;     // [C] (or null)
+  const bf16_t* xin;    // [M][C] the transformer's input (residual of proj_out)
+  float* gn_part;       // [(M / gn_seg)][C][2] (mean, M2) of y per row segment and channel (or null)
+  int gn_seg;           // 32, 64 or 128
   const bf16_t* x_end;  // CSK_DEBUG bounds
   const bf16_t* w1_end;
   const bf16_t* w2_end;
+  const bf16_t* wp_end;
   int M, I;
   float eps;
 };
@@ -62,6 +85,8 @@ struct FfArgs {
 #define FF_PIECES (FF_SLOT / 512)       // 1 KB DMA pieces per slot
 #define FF_PPW (FF_PIECES / FF_WAVES)   // pieces per wave per slot
 #define FF_IMAX 1280                    // b1 staged in LDS: 2 * I floats
+#define FF_ZLD 328                      // PROJ: elements per staged output row (656 B: 16-byte chunks stay aligned,
+                                        // the 8-byte fragment writes of 32 rows spread over 16 bank groups)
 
 template <int N>
 __device__ __forceinline__ void ff_vmcnt() {
@@ -94,7 +119,8 @@ __device__ __forceinline__ void ff_waitf(v4f (&b)[4]) {
 
 // PROBE (profiling builds, wrong results by design; csk_set_ff_probe): 1 = no
 // MFMAs, 2 = no GEGLU math, 4 = no weight DMA after the prologue (slots reused)
-template <int C, int PROBE = 0>
+// PROJ: proj_out in the tail (whole 128-row tiles only, host-checked)
+template <int C, int PROBE = 0, bool PROJ = false>
 __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs a) {
   constexpr int KS = C / 16;   // 16-deep k-steps of the GEGLU projection
   constexpr int NOT = C / 32;  // 32-wide output tiles
@@ -114,7 +140,8 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs
   const bool row_ok = row < a.M;
   const int I = a.I;
   const int nchunk = I / 32;
-  const int nslots = 3 * nchunk;
+  const int nff = 3 * nchunk;                      // slots of the feed-forward itself
+  const int nslots = nff + (PROJ ? NOT : 0);       // + one Wp slice [C][32] per 32 input channels
 
   // ---- LDS-DMA: this wave's piece i (of FF_PPW) of ring slot t ----
   auto dma_piece = [&](int t, int i) {
@@ -125,7 +152,9 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs
     // one contiguous 20 KB run, piece p its p-th KB
     const bf16_t* src = (kind < 2 ? a.w1 + (size_t)(2 * c + kind) * FF_SLOT : a.w2 + (size_t)c * FF_SLOT) +
                         512 * p + 8 * lane;
-    CSK_DCHECK(src + 8 <= (kind < 2 ? a.w1_end : a.w2_end), 91, t, I);
+    const bool tail = PROJ && t >= nff;  // the Wp slices follow the last W2 slice
+    if (tail) src = a.wp + (size_t)(t - nff) * FF_SLOT + 512 * p + 8 * lane;
+    CSK_DCHECK(src + 8 <= (tail ? a.wp_end : kind < 2 ? a.w1_end : a.w2_end), 91, t, I);
     __builtin_amdgcn_global_load_lds((ff_gptr_t)src, (ff_lptr_t)(base + 512 * p), 16, 0, 0);
   };
   auto dma_slot = [&](int t) {
@@ -279,13 +308,12 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs
     }
   };
 
-  // out^T += W2 slice (slot t) [H_a; H_b]^T: 2 k-steps x 10 output tiles;
-  // H_b = GEGLU(acc_b) is formed after MFMA GAT (the first 10 need only H_a)
-  auto w2_slice = [&](int t, const v8s& ha, v16f& acc_b, v4f (&bqb)[4]) {
+  // dst^T += slice [C][32] (slot t) [ha; hb]^T: 2 k-steps x 10 output tiles;
+  // mid() runs after MFMA GAT and may form hb (the first 10 need only ha)
+  auto slice = [&](int t, v16f (&dst)[NOT], const v8s& ha, v8s& hb, auto&& mid) {
     const unsigned sb = slot_base(t);
     constexpr int NR = 2 * NOT;
     v8s wf[NR];
-    v8s hb;
 #pragma unroll
     for (int i = 0; i < D; ++i) ff_ld(wf[i], sb + w2o[i / NOT] + (unsigned)((i % NOT) * 2048));
 #pragma unroll
@@ -293,14 +321,19 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs
       ff_wait(i + D - 1 < NR ? D - 1 : NR - 1 - i, wf[i]);
       const int o = i % NOT;
       if constexpr ((PROBE & 1) != 0) asm volatile("" ::"v"(wf[i]), "v"(ha), "v"(hb));
-      else out[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], i < NOT ? ha : hb, out[o], 0, 0, 0);
+      else dst[o] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], i < NOT ? ha : hb, dst[o], 0, 0, 0);
       if (i + D < NR) {
         const int i1 = i + D;
         ff_ld(wf[i1], sb + w2o[i1 / NOT] + (unsigned)((i1 % NOT) * 2048));
       }
       dma_hook(t, i);
-      if (i == GAT) hb = geglu(acc_b, bqb);
+      if (i == GAT) mid();
     }
+  };
+  // out^T += W2 slice (slot t) [H_a; H_b]^T; H_b = GEGLU(acc_b) is formed after MFMA GAT
+  auto w2_slice = [&](int t, const v8s& ha, v16f& acc_b, v4f (&bqb)[4]) {
+    v8s hb;
+    slice(t, out, ha, hb, [&] { hb = geglu(acc_b, bqb); });
   };
 
   // two chunks (6 slots, 3 pairs) per trip: barriers in front of t, t + 2, t + 4
@@ -320,6 +353,125 @@ __global__ __launch_bounds__(FF_WAVES * 64, 1) void ff_geglu_kernel(const FfArgs
     w2_slice(t + 5, ha, acc_b, bqb);
   }
 
+  auto u2f4 = [](const uint2& u, float (&f)[4]) {
+    f[0] = bf2f((bf16_t)(u.x & 0xffff));
+    f[1] = bf2f((bf16_t)(u.x >> 16));
+    f[2] = bf2f((bf16_t)(u.y & 0xffff));
+    f[3] = bf2f((bf16_t)(u.y >> 16));
+  };
+  if constexpr (PROJ) {
+    // ---- proj_out tail.  Every row is valid (whole tiles).  The loads below
+    // queue behind the Wp slots already in flight, so the counted waits of
+    // enter_pair only ever wait for more than they need. ----
+    uint2 xr[NOT][4], br[NOT][4], xi[NOT][4];
+#pragma unroll
+    for (int o = 0; o < NOT; ++o)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = 32 * o + 8 * q + 4 * h;
+        CSK_DCHECK(a.x + (size_t)row * C + n + 4 <= a.x_end, 95, row, a.M);
+        xr[o][q] = *reinterpret_cast<const uint2*>(a.x + (size_t)row * C + n);
+        br[o][q] = a.b2 ? *reinterpret_cast<const uint2*>(a.b2 + n) : make_uint2(0, 0);
+      }
+#pragma unroll
+    for (int o = 0; o < NOT; ++o)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = 32 * o + 8 * q + 4 * h;
+        xi[o][q] = *reinterpret_cast<const uint2*>(a.xin + (size_t)row * C + n);
+      }
+    // y = out + b2 + x rounded to bf16: out[o][8 s .. 8 s + 7] is the B fragment of k-step 32 o + 16 s
+    v8s yf[NOT][2];
+#pragma unroll
+    for (int o = 0; o < NOT; ++o) {
+      float v[16];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float rv[4], bb[4];
+        u2f4(xr[o][q], rv);
+        u2f4(br[o][q], bb);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[4 * q + r] = out[o][4 * q + r] + bb[r] + rv[r];
+      }
+      yf[o][0] = __builtin_bit_cast(v8s, pack8(v));
+      yf[o][1] = __builtin_bit_cast(v8s, pack8(v + 8));
+    }
+    v16f z[NOT];
+#pragma unroll
+    for (int o = 0; o < NOT; ++o)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) z[o][i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NOT; ++j) {
+      if ((j & 1) == 0) enter_pair(nff + j);  // nff is even: the pairs stay aligned
+      slice(nff + j, z, yf[j][0], yf[j][1], [] {});
+    }
+    // every wave is done with the ring: stage the rounded tile, wave w's 32 rows at w * 32 * FF_ZLD
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    bf16_t* zs = ring + wid * 32 * FF_ZLD;
+#pragma unroll
+    for (int o = 0; o < NOT; ++o)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float rv[4], bb[4];
+        u2f4(xi[o][q], rv);
+        u2f4(a.bp ? *reinterpret_cast<const uint2*>(a.bp + 32 * o + 8 * q + 4 * h) : make_uint2(0, 0), bb);
+        uint2 w;
+        w.x = pack2(z[o][4 * q] + bb[0] + rv[0], z[o][4 * q + 1] + bb[1] + rv[1]);
+        w.y = pack2(z[o][4 * q + 2] + bb[2] + rv[2], z[o][4 * q + 3] + bb[3] + rv[3]);
+        *reinterpret_cast<uint2*>(zs + r32 * FF_ZLD + 32 * o + 8 * q + 4 * h) = w;
+      }
+    __syncthreads();
+    // lane c < C / 8 owns channels 8 c .. 8 c + 7 of the slab: whole 640-byte rows per store
+    // instruction, and the two-pass (mean, M2) of the ROUNDED values over the 32 rows
+    float* st = reinterpret_cast<float*>(ring + FF_WAVES * 32 * FF_ZLD);  // [FF_WAVES][C][2]
+    if (lane < C / 8) {
+      bf16_t* yrow = a.y + (size_t)(m0 + wid * 32) * C + 8 * lane;
+      float sum[8], m2[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum[j] = m2[j] = 0.f;
+#pragma unroll 8
+      for (int r = 0; r < 32; ++r) {
+        const uint4 u = *reinterpret_cast<const uint4*>(zs + r * FF_ZLD + 8 * lane);
+        *reinterpret_cast<uint4*>(yrow + (size_t)r * C) = u;
+        float f[8];
+        unpack8(u, f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum[j] += f[j];
+      }
+      if (a.gn_part) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum[j] *= (1.0f / 32);
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) {
+          float f[8];
+          unpack8(*reinterpret_cast<const uint4*>(zs + r * FF_ZLD + 8 * lane), f);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float d = f[j] - sum[j];
+            m2[j] = __builtin_fmaf(d, d, m2[j]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          *reinterpret_cast<float2*>(st + ((size_t)wid * C + 8 * lane + j) * 2) = make_float2(sum[j], m2[j]);
+      }
+    }
+    if (!a.gn_part) return;
+    __syncthreads();
+    const int seg = a.gn_seg, per = seg / 32;  // slabs per segment, merged in slab order
+    for (int i = tid; i < (FF_ROWS / seg) * C; i += FF_WAVES * 64) {
+      const int n = i % C, sg = i / C;
+      float cnt = 0.f, mean = 0.f, q2 = 0.f;
+      for (int w = 0; w < per; ++w) {
+        const float2 pm = *reinterpret_cast<const float2*>(st + ((size_t)(sg * per + w) * C + n) * 2);
+        chan_combine(cnt, mean, q2, 32.f, pm.x, pm.y);
+      }
+      *reinterpret_cast<float2*>(a.gn_part + ((size_t)(m0 / seg + sg) * C + n) * 2) = make_float2(mean, q2);
+    }
+    return;
+  }
   // ---- epilogue: + b2 + residual x; accumulator rows 32 o + 8 q + 4 h + r of row `row` ----
   if (!row_ok) return;
   uint2 xr[NOT][4], br[NOT][4];
@@ -366,7 +518,7 @@ CSK_API int csk_ff_geglu_ok(int M, int C, int I) {
 CSK_API int csk_ff_geglu(void* y, const void* x, const void* gamma, const void* beta, const void* w1, const void* b1,
                          const void* w2, const void* b2, int M, int C, int I, float eps, hipStream_t stream) {
   if (!csk_ff_geglu_ok(M, C, I) || !x || !y || !gamma || !w1 || !w2 || x == y) return (int)hipErrorInvalidValue;
-  FfArgs a;
+  FfArgs a = {};
   a.x = (const bf16_t*)x;
   a.gamma = (const bf16_t*)gamma;
   a.beta = (const bf16_t*)beta;
@@ -388,5 +540,53 @@ CSK_API int csk_ff_geglu(void* y, const void* x, const void* gamma, const void* 
     case 4: ff_geglu_kernel<320, 4><<<grid, FF_WAVES * 64, 0, stream>>>(a); break;
     default: ff_geglu_kernel<320><<<grid, FF_WAVES * 64, 0, stream>>>(a); break;
   }
+  return (int)hipGetLastError();
+}
+
+// 1 when csk_ff_geglu_proj takes this shape: whole 128-row tiles, and GroupNorm
+// segments of gn_seg rows (0: no statistics) that never straddle a sample
+CSK_API int csk_ff_geglu_proj_ok(int M, int C, int I, int gn_seg, int rows_per_b) {
+  if (!csk_ff_geglu_ok(M, C, I) || M % FF_ROWS) return 0;
+  if (gn_seg == 0) return 1;
+  return ((gn_seg == 32 || gn_seg == 64 || gn_seg == 128) && rows_per_b > 0 && rows_per_b % gn_seg == 0 &&
+          M % rows_per_b == 0)
+             ? 1
+             : 0;
+}
+
+// z[M][C] = xin + Wp bf16(x + W2 GEGLU(W1 LN(x) + b1) + b2) + bp: the feed-forward
+// with the transformer's proj_out in its tail (wp packed by ops.pack_ff_proj), and
+// gn_part[M / gn_seg][C][2] = (mean, M2) of z per row segment and channel
+// (gn_part null / gn_seg 0: none).  z must alias neither x nor xin.
+CSK_API int csk_ff_geglu_proj(void* z, const void* x, const void* gamma, const void* beta, const void* w1,
+                              const void* b1, const void* w2, const void* b2, const void* wp, const void* bp,
+                              const void* xin, void* gn_part, int gn_seg, int rows_per_b, int M, int C, int I, float eps,
+                              hipStream_t stream) {
+  if (!gn_part) gn_seg = 0;
+  if (!csk_ff_geglu_proj_ok(M, C, I, gn_seg, rows_per_b) || !x || !z || !gamma || !w1 || !w2 || !wp || !xin ||
+      x == z || xin == z)
+    return (int)hipErrorInvalidValue;
+  FfArgs a = {};
+  a.x = (const bf16_t*)x;
+  a.gamma = (const bf16_t*)gamma;
+  a.beta = (const bf16_t*)beta;
+  a.w1 = (const bf16_t*)w1;
+  a.b1 = (const float*)b1;
+  a.w2 = (const bf16_t*)w2;
+  a.b2 = (const bf16_t*)b2;
+  a.y = (bf16_t*)z;
+  a.wp = (const bf16_t*)wp;
+  a.bp = (const bf16_t*)bp;
+  a.xin = (const bf16_t*)xin;
+  a.gn_part = (float*)gn_part;
+  a.gn_seg = gn_seg;
+  a.x_end = a.x + (size_t)M * C;
+  a.w1_end = a.w1 + (size_t)2 * I * C;
+  a.w2_end = a.w2 + (size_t)C * I;
+  a.wp_end = a.wp + (size_t)C * C;
+  a.M = M;
+  a.I = I;
+  a.eps = eps;
+  ff_geglu_kernel<320, 0, true><<<dim3(M / FF_ROWS), FF_WAVES * 64, 0, stream>>>(a);
   return (int)hipGetLastError();
 }

@@ -34,6 +34,24 @@
 //            |B2: Wo_h landed|  out-proj h  |B3: Wq_{h+1}, K/V_{h+1} landed|
 // so every transfer has at least one compute phase to land in, and the waits
 // are counted (vmcnt) — the prefetches stay in flight across B1 / B2.
+//
+// PRE variant (csk_xattn_block_pre): the self-attention out-projection is the
+// prologue, so its output x never reaches HBM:
+//
+//   x = bf16(h0 + O Wo1^T + bo1)      (O: the attention output, h0: its residual)
+//
+// x^T = Wo1 O^T runs on the same 16x16x32 MFMAs: B = the wave's O rows, loaded
+// from global exactly as the x fragments are, A = Wo1 rows from LDS, streamed
+// as C / 64 K-slices [C][64] through s_wq / s_wo as a double buffer (K / V of
+// head 0 in flight throughout; Wo / Wq' of head 0 follow into the buffers as
+// the last two slices retire).  The accumulators leave row fr, channels
+// 16 nt + 4 g + r on the lane: tiles (2 cs, 2 cs + 1), + bo1 + h0, rounded and
+// packed, are the Q projection's B fragment of k-step cs in the k-slot order
+// (4 g + r, 16 + 4 g + r) — the host permutes the columns of Wq' to that order
+// within each 32-block (ops.permute_xattn_q; colsum is unaffected) — and the
+// epilogue's residual, whose layout they share.  src_rows: O and h0 have
+// src_rows rows, row m reads row m % src_rows (both CFG halves from the
+// half-batch self-attention; K / V still follow m).  8 waves x 16 rows only.
 #include "attn_tile.h"
 
 typedef __attribute__((address_space(1))) const void* xa_gptr_t;
@@ -50,6 +68,12 @@ struct XattnArgs {
   bf16_t* y;            // [M][C]
   float* row_part;      // [M][2] (mean, M2) of y over C, or null
   const bf16_t* zero;   // zero page (DMA source of K / V padding rows)
+  // PRE variant: x = bf16(h0 + o wo1^T + bo1) instead of a.x (wq then column-permuted)
+  const bf16_t* o;      // [src_rows][C] attention output
+  const bf16_t* h0;     // [src_rows][C] residual of the out-projection
+  const bf16_t* wo1;    // [C][C] out-projection weight
+  const bf16_t* bo1;    // [C] or null
+  int src_rows;
   const bf16_t* x_end;  // CSK_DEBUG bounds
   const bf16_t* kv_end;
   int M, rows_per_b, Skv;
@@ -79,7 +103,7 @@ __device__ __forceinline__ v8s xa_pack8(const v4f& lo, const v4f& hi, float s) {
 // PROBE (profiling builds, wrong results by design; csk_set_xattn_probe): 1 = no
 // Q-projection MFMAs, 2 = no attention (S / softmax / PV), 4 = no out-projection
 // MFMAs, 8 = no per-head DMA (operands of head 0 reused)
-template <int C, int NW, int RT, int PROBE = 0>
+template <int C, int NW, int RT, int PROBE = 0, bool PRE = false>
 __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs a) {
   constexpr int H = C / 64, NCS = C / 32, NNT = C / 16, CPR = C / 8;
   constexpr int WQ = 64 * C, WO = C * 64, KVI = XA_KVR * 64;
@@ -114,15 +138,17 @@ __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs
       xa_dma_off(a.wq, (unsigned)((h * 64 + row) * C + 8 * (slot ^ (row & 7))), s_wq + 512 * p);
     }
   };
-  auto dma_wo = [&](int h) {
+  // columns 64 h .. 64 h + 63 of a [C][C] weight as a swizzled [C][64] image
+  auto dma_cols = [&](const bf16_t* w, int h, bf16_t* dst) {
 #pragma unroll
     for (int i = 0; i < NWO; ++i) {
       const int p = wid + NW * i;
       const int row = 8 * p + (lane >> 3), slot = lane & 7;
       CSK_DCHECK(row < C, 72, row, C);
-      xa_dma_off(a.wo, (unsigned)(row * C + h * 64 + 8 * (slot ^ at_key(row))), s_wo + 512 * p);
+      xa_dma_off(w, (unsigned)(row * C + h * 64 + 8 * (slot ^ at_key(row))), dst + 512 * p);
     }
   };
+  auto dma_wo = [&](int h) { dma_cols(a.wo, h, s_wo); };
   auto dma_kv = [&](int h, bf16_t* dst) {
 #pragma unroll
     for (int i = 0; i < NKV; ++i) {
@@ -143,10 +169,76 @@ __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs
     s_cb[i] = a.colsum[i];
     s_cb[C + i] = bf2f(a.bq[i]);
   }
+  v8s xf[RT][NCS];
+  if constexpr (PRE) {
+    // ---- x = bf16(h0 + O Wo1^T + bo1) in registers (every row is valid: whole tiles) ----
+    static_assert(WQ == WO && C % 64 == 0, "Wo1 K-slices double-buffer through s_wq / s_wo");
+    constexpr int NKS = C / 64;
+    dma_kv(0, s_kv0);  // oldest transfer: landed before any slice wait returns
+    v8s of0[RT][NCS];
+    uint2 hres[RT][NNT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int ms = (row_w + rt * 16 + fr) % a.src_rows;
+      CSK_DCHECK(a.o + (size_t)ms * C + C <= a.x_end, 75, ms, a.src_rows);
+#pragma unroll
+      for (int cs = 0; cs < NCS; ++cs)
+        of0[rt][cs] = __builtin_bit_cast(v8s, *reinterpret_cast<const uint4*>(a.o + (size_t)ms * C + 32 * cs + 8 * g));
+#pragma unroll
+      for (int nt = 0; nt < NNT; ++nt)
+        hres[rt][nt] = *reinterpret_cast<const uint2*>(a.h0 + (size_t)ms * C + 16 * nt + 4 * g);
+    }
+    dma_cols(a.wo1, 0, s_wq);
+    dma_cols(a.wo1, 1, s_wo);
+    v4f xa[RT][NNT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int nt = 0; nt < NNT; ++nt) xa[rt][nt] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      // slice ks has landed; the newer transfer (slice ks + 1, or Wo of head 0) stays in flight
+      xa_vmcnt<NWO>();
+      __builtin_amdgcn_s_barrier();
+      const bf16_t* buf = (ks & 1) ? s_wo : s_wq;
+#pragma unroll
+      for (int nt = 0; nt < NNT; ++nt) {
+#pragma unroll
+        for (int ds = 0; ds < 2; ++ds) {
+          const v8s wf = *reinterpret_cast<const v8s*>(buf + at_off64(16 * nt + fr, 4 * ds + g));
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt)
+            xa[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, of0[rt][2 * ks + ds], xa[rt][nt], 0, 0, 0);
+        }
+      }
+      // every wave is done with the buffer: the next slice, then head 0's Wo / Wq', land there
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (ks + 2 < NKS) dma_cols(a.wo1, ks + 2, (ks & 1) ? s_wo : s_wq);
+      else if (ks & 1) dma_wo(0);
+      else dma_wq(0);
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int nt = 0; nt < NNT; ++nt) {
+        const uint2 u = hres[rt][nt];
+        const uint2 ub = a.bo1 ? *reinterpret_cast<const uint2*>(a.bo1 + 16 * nt + 4 * g) : make_uint2(0, 0);
+        const float rv[4] = {bf2f((bf16_t)(u.x & 0xffff)), bf2f((bf16_t)(u.x >> 16)), bf2f((bf16_t)(u.y & 0xffff)),
+                             bf2f((bf16_t)(u.y >> 16))};
+        const float bv[4] = {bf2f((bf16_t)(ub.x & 0xffff)), bf2f((bf16_t)(ub.x >> 16)), bf2f((bf16_t)(ub.y & 0xffff)),
+                             bf2f((bf16_t)(ub.y >> 16))};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xa[rt][nt][r] = xa[rt][nt][r] + bv[r] + rv[r];
+      }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int cs = 0; cs < NCS; ++cs) xf[rt][cs] = xa_pack8(xa[rt][2 * cs], xa[rt][2 * cs + 1], 1.0f);
+  } else {
   dma_wq(0);
   dma_wo(0);
   dma_kv(0, s_kv0);
-  v8s xf[RT][NCS];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int m = row_w + rt * 16 + fr;
@@ -159,6 +251,7 @@ __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs
       }
       xf[rt][cs] = __builtin_bit_cast(v8s, u);
     }
+  }
   }
   // LayerNorm statistics of the two rows this lane holds (four lane groups x NCS x 8)
   float mean[RT], rstd[RT];
@@ -325,6 +418,14 @@ __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs
   // x as far as the compiler knows, so loads left at their use each waited one
   // memory latency behind the previous store (20 per row tile).
   uint2 xres[RT][NNT], bres[NNT];
+  if constexpr (PRE) {
+    // the residual is unpacked from the fragments HERE: left to itself the compiler
+    // unpacks them to fp32 in the prologue and carries 80 more registers through the heads
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int cs = 0; cs < NCS; ++cs) asm volatile("" : "+v"(xf[rt][cs]));
+  }
 #pragma unroll
   for (int nt = 0; nt < NNT; ++nt) {
     bres[nt] = make_uint2(0, 0);
@@ -336,7 +437,12 @@ __global__ __launch_bounds__(NW * 64, 1) void xattn_block_kernel(const XattnArgs
 #pragma unroll
     for (int nt = 0; nt < NNT; ++nt) {
       xres[rt][nt] = make_uint2(0, 0);
-      if (m < a.M) xres[rt][nt] = *reinterpret_cast<const uint2*>(a.x + (size_t)m * C + 16 * nt + 4 * g);
+      if constexpr (PRE) {  // x lives in the Q projection's fragments: tile nt is half nt & 1 of k-step nt / 2
+        const uint4 u = __builtin_bit_cast(uint4, xf[rt][nt >> 1]);
+        xres[rt][nt] = (nt & 1) ? make_uint2(u.z, u.w) : make_uint2(u.x, u.y);
+      } else if (m < a.M) {
+        xres[rt][nt] = *reinterpret_cast<const uint2*>(a.x + (size_t)m * C + 16 * nt + 4 * g);
+      }
     }
   }
 #pragma unroll
@@ -424,7 +530,7 @@ CSK_API int csk_xattn_block(void* y, const void* x, const void* wq, const void* 
   if (!csk_zero_ptr()) return (int)hipErrorNotInitialized;
   if (Skv < 1 || Skv > 80 || rows_per_b % XA_BM != 0 || M % rows_per_b != 0 || M / rows_per_b > Bc)
     return (int)hipErrorInvalidValue;
-  XattnArgs a;
+  XattnArgs a = {};
   a.x = (const bf16_t*)x;
   a.wq = (const bf16_t*)wq;
   a.colsum = (const float*)colsum;
@@ -450,5 +556,51 @@ CSK_API int csk_xattn_block(void* y, const void* x, const void* wq, const void* 
       break;
     default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
+}
+
+// 1 when csk_xattn_block_pre takes this shape
+CSK_API int csk_xattn_block_pre_ok(int M, int C, int rows_per_b, int Bc, int Skv, int src_rows) {
+  return (C == 320 && Skv >= 1 && Skv <= 80 && rows_per_b > 0 && rows_per_b % XA_BM == 0 && M > 0 &&
+          M % rows_per_b == 0 && M / rows_per_b <= Bc && src_rows > 0 && M % src_rows == 0)
+             ? 1
+             : 0;
+}
+
+// csk_xattn_block on x = bf16(h0 + o wo1^T + bo1), formed in the prologue and never
+// stored: o, h0 [src_rows][C] (row m reads row m % src_rows), wo1 [C][C], bo1 [C] or
+// null; wq is the folded query weight with its columns permuted by
+// ops.permute_xattn_q.  y must alias neither o nor h0.
+CSK_API int csk_xattn_block_pre(void* y, const void* o, const void* h0, const void* wo1, const void* bo1,
+                                const void* wq, const void* colsum, const void* bq, const void* kv, const void* wo,
+                                const void* bo, void* row_part, int M, int C, int rows_per_b, int Bc, int Skv,
+                                int src_rows, float eps, float scale, hipStream_t stream) {
+  if (!csk_zero_ptr()) return (int)hipErrorNotInitialized;
+  if (!csk_xattn_block_pre_ok(M, C, rows_per_b, Bc, Skv, src_rows) || !y || !o || !h0 || !wo1 || !wq || !colsum ||
+      !bq || !kv || !wo || y == o || y == h0)
+    return (int)hipErrorInvalidValue;
+  XattnArgs a = {};
+  a.o = (const bf16_t*)o;
+  a.h0 = (const bf16_t*)h0;
+  a.wo1 = (const bf16_t*)wo1;
+  a.bo1 = (const bf16_t*)bo1;
+  a.src_rows = src_rows;
+  a.wq = (const bf16_t*)wq;
+  a.colsum = (const float*)colsum;
+  a.bq = (const bf16_t*)bq;
+  a.kv = (const bf16_t*)kv;
+  a.wo = (const bf16_t*)wo;
+  a.bo = (const bf16_t*)bo;
+  a.y = (bf16_t*)y;
+  a.row_part = (float*)row_part;
+  a.zero = csk_zero_ptr();
+  a.x_end = a.o + (size_t)src_rows * C;
+  a.kv_end = a.kv + (size_t)Bc * Skv * 2 * C;
+  a.M = M;
+  a.rows_per_b = rows_per_b;
+  a.Skv = Skv;
+  a.eps = eps;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  xattn_block_kernel<320, 8, 1, 0, true><<<dim3(M / XA_BM), 8 * 64, 0, stream>>>(a);
   return (int)hipGetLastError();
 }

@@ -77,6 +77,14 @@ def apply_arm(arm):
         hip_ops.XATTN_FUSED = arm == "xa1"
     elif arm in ("ff0", "ff1"):  # C = 320 feed-forward: two GEMMs (0) / one fused kernel (1, ff.hip)
         hip_ops.FF_FUSED = arm == "ff1"
+    elif arm in ("xpre0", "xpre1"):  # C = 320 self-attention out-projection: own GEMM (0) / prologue of the fused block (1)
+        hip_ops.XATTN_PRE = arm == "xpre1"
+    elif arm in ("xdup0", "xdup1"):  # CFG-shared first block's cross-attention: unfused chain (0) / one fused launch (1)
+        hip_ops.XATTN_DUP = arm == "xdup1"
+    elif arm in ("xtail0", "xtail1"):  # all three: xpre + xdup + ffp
+        hip_ops.XATTN_PRE = hip_ops.XATTN_DUP = hip_ops.FF_PROJ = arm == "xtail1"
+    elif arm in ("ffp0", "ffp1"):  # C = 320 proj_out: its own GEMM (0) / the tail of the fused feed-forward (1)
+        hip_ops.FF_PROJ = arm == "ffp1"
     elif arm in ("xin0", "xin1"):  # C = 320 transformer input: GN + proj_in + QKV GEMMs (0) / one kernel (1, xin.hip)
         hip_ops.XIN_FUSED = arm == "xin1"
     elif arm in ("lnoff", "lnon"):

@@ -55,6 +55,10 @@ def flops_of(name, a):
     if name == "csk_xattn_block":
         M, C, rpb, Bc, Skv = a[9:14]
         return (f"xattn block M{M} C{C} Skv{Skv}", 2.0 * M * C * C * 2 + 4.0 * M * Skv * C, None)
+    if name == "csk_xattn_block_pre":  # ... with the self-attention out-projection as its prologue
+        M, C, rpb, Bc, Skv, src = a[12:18]
+        return (f"xattn block + out-proj M{M} C{C} Skv{Skv}" + (f" src{src}" if src != M else ""),
+                2.0 * M * C * C * 3 + 4.0 * M * Skv * C, None)
     if name == "csk_conv_tile":  # persistent halo-tile 3x3 conv (conv_tile.hip)
         B, H, W, Cin, Cout = a[5:10]
         return f"conv-tile B{B} {H}x{W} s1 {Cin}->{Cout} k3", 2.0 * B * H * W * Cout * 9 * Cin, None
@@ -66,6 +70,10 @@ def flops_of(name, a):
     if name == "csk_ff_geglu":  # fused feed-forward (ff.hip)
         M, C, inner = a[8:11]
         return f"ff fused M{M} C{C} I{inner}", 2.0 * M * C * 2 * inner + 2.0 * M * inner * C, None
+    if name == "csk_ff_geglu_proj":  # ... with the transformer's proj_out in its tail
+        M, C, inner = a[14:17]
+        return (f"ff fused + proj_out M{M} C{C} I{inner}", 2.0 * M * C * 2 * inner + 2.0 * M * inner * C + 2.0 * M * C * C,
+                None)
     return name, 0.0, None
 
 
