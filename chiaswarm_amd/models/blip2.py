@@ -27,9 +27,15 @@ LayerNorm, GEMM epilogues):
 
 Greedy decode with transformers' default ``max_length=20`` (OPT: counted on the
 text part, ``</s>`` + prompt + generated; T5: decoder tokens), stopping at the
-eos token.  Every step re-runs the (short) decoder sequence: at that size each
-GEMM streams its weights once either way, so a KV cache would save no HBM
-traffic.  The original-T5 (ReLU FFN) language models are refused.
+eos token.  Decode is KV-cached for all three language models: OPT prefills
+``[queries; </s>; prompt]`` through the GEMM path once (``prefill``) and then
+runs one token per ``decode_step`` through the decode kernels (``ops.gemv`` with
+the LayerNorm prologue, ``ops.decode_attention`` at head dim 80 for OPT-2.7B),
+five launches a layer replayed from one hipGraph; Flan-T5 does the same through
+``T5Seq2Seq.begin_decode`` / ``decode_step``, Vicuna through ``LlamaLM``.
+``use_cache=False`` (``CSK_DECODE=0``) keeps the loops that re-run the whole
+sequence for every token.  The original-T5 (ReLU FFN) language models are
+refused.
 """
 from __future__ import annotations
 
@@ -41,9 +47,10 @@ import torch
 import torch.nn as nn
 from PIL import Image
 
+from .. import ops
 from .layers import LayerNorm, Linear
 from .llama import LlamaConfig, LlamaLM
-from .t5 import T5Config, T5Seq2Seq
+from .t5 import CACHE_ROUND, T5Config, T5Seq2Seq
 from .transformer import PostLNBlock, PreLNBlock, ViT
 
 MEAN = np.array([0.48145466, 0.4578275, 0.40821073], np.float32)
@@ -280,6 +287,7 @@ class Blip2Captioner(nn.Module):
             self.q_pos = nn.Embedding(cfg.q_max_pos, cfg.q_dim)
             self.qtext = nn.ModuleList([_TextFFN(cfg) for _ in range(cfg.q_depth)])
         self.language_projection = Linear(cfg.q_dim, cfg.lm_dim)
+        self.cache = None  # the OPT language model's K/V cache (new_cache)
         if cfg.lm_type == "llama":
             self.llama = LlamaLM(cfg.llama)
             return
@@ -346,27 +354,126 @@ class Blip2Captioner(nn.Module):
         h = self.lm_ln(x[:, -1:])
         return (h.float() @ self.embed_tokens.weight.float().t())[0, -1]
 
+    # ---- KV-cached OPT decode --------------------------------------------------
+    def new_cache(self, capacity: int):
+        """(Re)use the persistent per-layer [1, cap, H, dh] K/V buffers of the OPT
+        language model; ``cap`` is ``capacity`` rounded up to a multiple of
+        ``CACHE_ROUND``.  Buffers that are large enough are kept (a captured
+        decode graph stays valid across generations), a reallocation drops the
+        graph."""
+        if self.cfg.lm_type != "opt":
+            raise ValueError("Blip2Captioner.new_cache is the OPT language model's: T5Seq2Seq / LlamaLM have their own")
+        p, a = self.embed_tokens.weight, self.lm[0].attn
+        kv = getattr(self, "_kv", None)
+        if kv is None or kv[0][0].shape[1] < capacity or kv[0][0].device != p.device or kv[0][0].dtype != p.dtype:
+            cap = -(-max(int(capacity), 1) // CACHE_ROUND) * CACHE_ROUND
+            shape = (1, cap, a.heads, a.dh)
+            self._kv = [(torch.zeros(shape, device=p.device, dtype=p.dtype),
+                         torch.zeros(shape, device=p.device, dtype=p.dtype)) for _ in self.lm]
+            self._graph = None
+        self.cache = self._kv
+
+    @property
+    def cache_capacity(self) -> int:
+        return 0 if self.cache is None else self.cache[0][0].shape[1]
+
+    @torch.no_grad()
+    def prefill(self, prefix: torch.Tensor, ids: list[int]) -> torch.Tensor:
+        """``text_logits`` that also leaves the keys and values of every position
+        of [prefix embeddings; embed(ids)] in the cache (grown if it is missing
+        or too small): the GEMM path, run once per generation."""
+        dev = self.embed_tokens.weight.device
+        x = torch.cat([prefix, self.embed_tokens(torch.tensor([ids], device=dev))], 1)
+        s = x.shape[1]
+        if self.cache is None or self.cache_capacity < s or self.cache[0][0].device != x.device:
+            self.new_cache(s)
+        x = x + self.embed_positions.weight[2: 2 + s][None]
+        for blk, kv in zip(self.lm, self.cache):
+            x = blk(x, causal=True, cache=kv)
+        h = self.lm_ln(x[:, -1:])
+        return (h.float() @ self.embed_tokens.weight.float().t())[0, -1]
+
+    @torch.no_grad()
+    def _decode_fn(self, ids, pos_t, len_t):
+        x = self.embed_tokens(ids) + self.embed_positions(pos_t + 2)  # learned positions with offset 2
+        for blk, kv in zip(self.lm, self.cache):
+            x = blk.decode(x, kv, pos_t, len_t)
+        nf = self.lm_ln
+        return ops.gemv(x[:, -1], self.embed_tokens.weight, ln=(nf.weight, nf.bias, nf.eps)).float()[0]
+
+    @torch.no_grad()
+    def decode_step(self, token: int, pos: int) -> torch.Tensor:
+        """OPT next-token logits [vocab] after appending ``token`` at position
+        ``pos`` of the whole sequence (image queries included; positions
+        [0, pos) filled by ``prefill`` / earlier steps).  On the GPU the whole
+        step replays from one hipGraph; the returned tensor is then overwritten
+        by the next step."""
+        if self.cache is None or not 0 <= int(pos) < min(self.cache_capacity, self.cfg.max_pos):
+            raise ValueError(f"Blip2Captioner.decode_step: position {pos} outside the cache (capacity "
+                             f"{self.cache_capacity}) or the {self.cfg.max_pos} positions: call new_cache / prefill "
+                             "first")
+        dev = self.embed_tokens.weight.device
+        st = getattr(self, "_dstate", None)
+        if st is None or st[0].device != dev:
+            st = (torch.zeros(1, 1, dtype=torch.long, device=dev), torch.zeros(1, dtype=torch.long, device=dev),
+                  torch.zeros(1, dtype=torch.int32, device=dev))
+            self._dstate = st
+            self._graph = None
+        ids, pos_t, len_t = st
+        ids.fill_(int(token))
+        pos_t.fill_(int(pos))
+        len_t.fill_(int(pos) + 1)
+        from ..pipelines.graphs import CapturedCall, graphs_enabled
+
+        if not graphs_enabled(dev):
+            return self._decode_fn(ids, pos_t, len_t)
+        g = getattr(self, "_graph", None)
+        if g is None:
+            g = CapturedCall(self._decode_fn, ids=ids, pos_t=pos_t, len_t=len_t)
+            self._graph = g
+        return g.run(ids=ids, pos_t=pos_t, len_t=len_t)
+
     @torch.no_grad()
     def generate(self, image: Image.Image, prefix_ids: list[int], max_new_tokens: int | None = None,
                  max_length: int = 20, qtext_ids: list[int] | None = None, use_cache: bool | None = None) -> list[int]:
         """Greedy decode from ``</s> + prefix`` after the image queries; returns
-        prefix + generated ids (without the leading ``</s>``).  ``use_cache``
-        (Vicuna-LLaMA only): see ``_generate_llama``."""
+        prefix + generated ids (without the leading ``</s>``).  One ``prefill``
+        of ``[queries; </s>; prefix]``, then one KV-cached ``decode_step`` per
+        token; ``use_cache=False`` (or ``CSK_DECODE=0`` in the environment when
+        it is left at None) re-runs the whole sequence through ``text_logits``
+        for every token instead.  Flan-T5 / Vicuna: ``_generate_t5`` /
+        ``_generate_llama``."""
         if self.cfg.lm_type == "t5":
-            return self._generate_t5(image, prefix_ids, max_new_tokens, max_length, qtext_ids)
+            return self._generate_t5(image, prefix_ids, max_new_tokens, max_length, qtext_ids, use_cache)
         if self.cfg.lm_type == "llama":
             return self._generate_llama(image, prefix_ids, max_new_tokens, max_length, qtext_ids, use_cache)
         if max_new_tokens is None:
             max_new_tokens = max(0, max_length - 1 - len(prefix_ids))
+        if use_cache is None:
+            use_cache = os.environ.get("CSK_DECODE", "1") == "1"
         prefix = self.image_prefix(self.preprocess(image).to(self.embed_tokens.weight.device))
         ids = [self.cfg.bos_id] + list(prefix_ids)
         out = []
-        for _ in range(max_new_tokens):
-            nxt = int(self.text_logits(prefix, ids).argmax())
+        if not use_cache:
+            for _ in range(max_new_tokens):
+                nxt = int(self.text_logits(prefix, ids).argmax())
+                if nxt == self.cfg.eos_id:
+                    break
+                ids.append(nxt)
+                out.append(nxt)
+            return list(prefix_ids) + out
+        if max_new_tokens == 0:
+            return list(prefix_ids)
+        n = prefix.shape[1] + len(ids)
+        self.new_cache(n + max_new_tokens)
+        logits = self.prefill(prefix, ids)
+        for i in range(max_new_tokens):
+            nxt = int(logits.argmax())
             if nxt == self.cfg.eos_id:
                 break
-            ids.append(nxt)
             out.append(nxt)
+            if i + 1 < max_new_tokens:
+                logits = self.decode_step(nxt, n + i)
         return list(prefix_ids) + out
 
     @torch.no_grad()
@@ -376,16 +483,35 @@ class Blip2Captioner(nn.Module):
         ids = torch.tensor([list(prompt_ids) + [self.cfg.eos_id]], device=prefix.device)
         return t5.encode(torch.cat([prefix, t5.shared(ids).to(prefix.dtype)], 1))
 
-    def _generate_t5(self, image, prompt_ids, max_new_tokens, max_length, qtext_ids=None) -> list[int]:
+    def _generate_t5(self, image, prompt_ids, max_new_tokens, max_length, qtext_ids=None,
+                     use_cache=None) -> list[int]:
         """Greedy decode from the decoder start token; returns the generated ids
-        (the prompt lives in the encoder)."""
+        (the prompt lives in the encoder).  One ``begin_decode`` (every layer's
+        cross-attention K/V of the encoder states, projected once), then one
+        KV-cached ``decode_step`` per token, the first of them on the start
+        token at position 0.  ``use_cache=False`` (or ``CSK_DECODE=0`` in the
+        environment when it is left at None) re-runs the decoder over its whole
+        prefix through ``decode_logits`` for every token instead."""
         if max_new_tokens is None:
             max_new_tokens = max(0, max_length - 1)
+        if use_cache is None:
+            use_cache = os.environ.get("CSK_DECODE", "1") == "1"
         prefix = self.image_prefix(self.preprocess(image).to(self.t5.shared.weight.device), qtext_ids)
         enc = self.t5_encoder_states(prefix, prompt_ids)
         ids = [self.cfg.bos_id]
-        for _ in range(max_new_tokens):
-            nxt = int(self.t5.decode_logits(enc, ids).argmax())
+        if not use_cache:
+            for _ in range(max_new_tokens):
+                nxt = int(self.t5.decode_logits(enc, ids).argmax())
+                if nxt == self.cfg.eos_id:
+                    break
+                ids.append(nxt)
+            return ids[1:]
+        if max_new_tokens == 0:
+            return []
+        self.t5.new_cache(max_new_tokens, enc.shape[1])
+        self.t5.begin_decode(enc)
+        for i in range(max_new_tokens):
+            nxt = int(self.t5.decode_step(ids[-1], i).argmax())
             if nxt == self.cfg.eos_id:
                 break
             ids.append(nxt)

@@ -12,6 +12,14 @@ kv_lens=)``, csrc/kernels/attn_bias.hip) on [B, S, H, D] views of the
 projections: the fp32 bias is added to the unscaled scores in the kernel and
 the padding mask travels as per-sample key counts.  CPU tensors keep the plain
 fp32 torch formula (the transformers-parity tests run there).
+
+``T5Seq2Seq`` greedy decode is KV-cached: ``begin_decode`` projects every
+decoder layer's cross-attention K/V of the encoder output once, ``decode_step``
+runs one token through the decode kernels (``ops.gemv`` / ``ops.gemv_glu`` with
+the RMSNorm prologues, ``ops.decode_attention`` with the self-attention append
+and the relative-position bias as a distance-indexed table), eight launches a
+layer, replayed from one hipGraph.  ``decode_logits`` re-runs a whole prefix
+without a cache (the A/B of tools/captiondecodebench.py).
 """
 from __future__ import annotations
 
@@ -104,6 +112,27 @@ class _SelfAttention(nn.Module):
         self.o = Linear(inner, c.d_model, bias=False)
         if has_bias:
             self.relative_attention_bias = nn.Embedding(c.buckets, c.heads)
+
+    def fuse(self, names):
+        """One weight for the projections ``names`` (decoder self-attention:
+        q, k, v for the decode step's GEMV; cross-attention: k, v for the
+        one-off encoder projection); their weights become row-range views of it
+        (models/llama.py ``_Attn.prepare``), so nothing is resident twice and
+        state-dict names do not change.  Rebuilt if the parameters moved
+        (device, dtype or storage); returns (weight, rebuilt)."""
+        projs = [getattr(self, n) for n in names]
+        w, p0 = getattr(self, "w_fused", None), projs[0].weight
+        if (w is not None and w.device == p0.device and w.dtype == p0.dtype
+                and all(p.weight.untyped_storage().data_ptr() == w.untyped_storage().data_ptr() for p in projs)):
+            return w, False
+        w = torch.cat([p.weight.detach() for p in projs], 0)
+        r = 0
+        for p in projs:
+            n = p.weight.shape[0]
+            p.weight.data = w[r:r + n]
+            r += n
+        self.w_fused = w
+        return w, True
 
     def position_bias(self, s, device, bidirectional=True):
         pos = torch.arange(s, device=device)
@@ -230,13 +259,17 @@ class _DecBlock(nn.Module):
         self.layer = nn.ModuleList([_DecSelfLayer(c, has_bias), _CrossLayer(c), _FFLayer(c)])
 
 
+CACHE_ROUND = 256  # new_cache rounds both capacities up to a multiple of this
+
+
 class T5Seq2Seq(nn.Module):
     """T5 v1.1 / Flan-T5 encoder-decoder (transformers ``T5ForConditionalGeneration``
     parameter names: ``shared``, ``encoder.*``, ``decoder.*``, ``lm_head``), for
     BLIP-2's Flan-T5 language models.  The encoder takes input EMBEDDINGS (BLIP-2
-    puts the projected image queries ahead of the prompt); the decoder re-runs
-    its (short) prefix each greedy step with the causal relative-position bias
-    and cross-attention over the encoder output."""
+    puts the projected image queries ahead of the prompt).  ``decode_logits``
+    re-runs the decoder over its (short) prefix with the causal relative-position
+    bias and cross-attention over the encoder output; ``new_cache`` /
+    ``begin_decode`` / ``decode_step`` are the KV-cached form of the same step."""
 
     def __init__(self, c: T5Config, dec_layers: int | None = None, tie_embeddings: bool = False):
         super().__init__()
@@ -251,6 +284,7 @@ class T5Seq2Seq(nn.Module):
         self.decoder.final_layer_norm = T5RMSNorm(c.d_model, c.eps)
         self.lm_head = Linear(c.d_model, c.vocab, bias=False)
         self.checkpoint_ignore = ("encoder.embed_tokens.", "decoder.embed_tokens.")
+        self.cache = None
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, mask: torch.Tensor | None = None) -> torch.Tensor:
@@ -283,6 +317,130 @@ class T5Seq2Seq(nn.Module):
         if self.tie:  # tied head (original T5): transformers rescales by d_model^-0.5
             h = (h.float() * self.cfg.d_model ** -0.5).to(h.dtype)
         return self.lm_head(h).float()[0, -1]
+
+
+    # ---- KV-cached decode ----------------------------------------------------
+    def new_cache(self, dec_capacity: int, enc_capacity: int):
+        """(Re)use the persistent buffers of the cached decode: per decoder
+        layer a self-attention K/V pair [1, cap, H, d_kv] and a cross-attention
+        buffer [1, enc_cap, 2, H, d_kv] (K at index 0, V at 1), and the fp32
+        [H, cap] table of the self-attention bias by distance (entry d: the
+        bias of the key d positions behind the query).  Capacities are rounded
+        up to multiples of ``CACHE_ROUND``; buffers that are large enough are
+        kept (a captured decode graph stays valid across generations), a
+        reallocation drops the graph."""
+        c, p = self.cfg, self.lm_head.weight
+        kv, xkv = getattr(self, "_kv", None), getattr(self, "_xkv", None)
+        if (kv is None or kv[0][0].shape[1] < dec_capacity or xkv[0].shape[1] < enc_capacity
+                or kv[0][0].device != p.device or kv[0][0].dtype != p.dtype):
+            cap, ecap = (-(-max(int(n), 1) // CACHE_ROUND) * CACHE_ROUND for n in (dec_capacity, enc_capacity))
+            if kv is not None and kv[0][0].device == p.device:  # never shrink either buffer
+                cap, ecap = max(cap, kv[0][0].shape[1]), max(ecap, xkv[0].shape[1])
+            n = len(self.decoder.block)
+            z = lambda *shape: torch.zeros(shape, device=p.device, dtype=p.dtype)  # noqa: E731
+            self._kv = [(z(1, cap, c.heads, c.d_kv), z(1, cap, c.heads, c.d_kv)) for _ in range(n)]
+            self._xkv = [z(1, ecap, 2, c.heads, c.d_kv) for _ in range(n)]
+            self._enc_len = torch.zeros(1, dtype=torch.int32, device=p.device)
+            self._bias_tab = torch.zeros(c.heads, cap, dtype=torch.float32, device=p.device)
+            self._bias_key = None
+            self._graph = None
+        self.cache = self._kv
+        self._ensure_bias_table()
+
+    def _ensure_bias_table(self):
+        """Fill the distance table from decoder block 0's relative_attention_bias
+        (in place: a captured graph reads this tensor) when it is new or the
+        embedding moved or was written."""
+        w = self.decoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
+        key = (w.data_ptr(), w.device, w.dtype, w._version)
+        if self._bias_key != key:
+            c = self.cfg
+            d = torch.arange(self._bias_tab.shape[1], device=self._bias_tab.device)
+            bucket = relative_position_bucket(-d, c.buckets, c.max_distance, bidirectional=False)
+            self._bias_tab.copy_(w.detach().to(self._bias_tab.device)[bucket].float().t())
+            self._bias_key = key
+
+    @property
+    def cache_capacity(self) -> int:
+        return 0 if self.cache is None else self.cache[0][0].shape[1]
+
+    @torch.no_grad()
+    def begin_decode(self, enc: torch.Tensor, enc_mask: torch.Tensor | None = None):
+        """Start a generation over encoder states ``enc`` [1, T, d_model]: one
+        GEMM per decoder layer against its fused [k; v] cross-attention weight
+        fills the cross buffers, and the device-side encoder length is set to
+        T, or to the number of set entries of the PREFIX mask ``enc_mask``
+        [1, T] (``key_lens``).  The self-attention cache restarts at position 0
+        (``decode_step(start_token, 0)``)."""
+        t = enc.shape[1]
+        if (self.cache is None or self._xkv[0].shape[1] < t or self._xkv[0].device != enc.device
+                or self._xkv[0].dtype != self.lm_head.weight.dtype):
+            self.new_cache(max(self.cache_capacity, 1), t)
+        c = self.cfg
+        for blk, xkv in zip(self.decoder.block, self._xkv):
+            w, rebuilt = blk.layer[1].EncDecAttention.fuse(("k", "v"))
+            xkv[:, :t].copy_(ops.gemm(enc, w, None).view(1, t, 2, c.heads, c.d_kv))
+        if enc_mask is None:
+            self._enc_len.fill_(t)
+        else:
+            self._enc_len.copy_(key_lens(enc_mask))
+
+    @torch.no_grad()
+    def _decode_fn(self, ids, pos_t, len_t):
+        c = self.cfg
+        inner = c.heads * c.d_kv
+        x = self.shared(ids).to(self.lm_head.weight.dtype)  # [1, 1, d_model]
+        for blk, kv, xkv in zip(self.decoder.block, self.cache, self._xkv):
+            sa, ca, ff = blk.layer
+            a, e, d = sa.SelfAttention, ca.EncDecAttention, ff.DenseReluDense
+            qkv = ops.gemv(x, a.fuse(("q", "k", "v"))[0], rms=(sa.layer_norm.weight, sa.layer_norm.eps))
+            qkv = qkv.view(1, 1, 3, c.heads, c.d_kv)
+            o = ops.decode_attention(qkv[:, :, 0], kv[0], kv[1], 1.0, len_t, k_new=qkv[:, :, 1], v_new=qkv[:, :, 2],
+                                     pos=pos_t, rel_bias=self._bias_tab)  # T5: no 1/sqrt(d) scaling
+            x = ops.gemv(o.reshape(1, 1, inner), a.o.weight, residual=x)
+            q = ops.gemv(x, e.q.weight, rms=(ca.layer_norm.weight, ca.layer_norm.eps)).view(1, 1, c.heads, c.d_kv)
+            o = ops.decode_attention(q, xkv[:, :, 0], xkv[:, :, 1], 1.0, self._enc_len)
+            x = ops.gemv(o.reshape(1, 1, inner), e.o.weight, residual=x)
+            h = ops.gemv_glu(x, d.wi_0.weight, d.wi_1.weight, act="gelu_tanh",
+                             rms=(ff.layer_norm.weight, ff.layer_norm.eps))
+            x = ops.gemv(h, d.wo.weight, residual=x)
+        nf = self.decoder.final_layer_norm
+        logits = ops.gemv(x[:, -1], self.lm_head.weight, rms=(nf.weight, nf.eps)).float()[0]
+        return logits * c.d_model ** -0.5 if self.tie else logits  # tied head: see decode_logits
+
+    @torch.no_grad()
+    def decode_step(self, token: int, pos: int) -> torch.Tensor:
+        """Next-token logits [vocab] after appending decoder ``token`` at position
+        ``pos`` (the start token at 0) of the self-attention cache, over the
+        encoder states of the last ``begin_decode``.  On the GPU the whole step
+        replays from one hipGraph; the returned tensor is then overwritten by
+        the next step."""
+        if self.cache is None or not 0 <= int(pos) < self.cache_capacity:
+            raise ValueError(f"T5Seq2Seq.decode_step: position {pos} outside the cache (capacity "
+                             f"{self.cache_capacity}): call new_cache / begin_decode first")
+        dev = self.lm_head.weight.device
+        if any([blk.layer[0].SelfAttention.fuse(("q", "k", "v"))[1] for blk in self.decoder.block]):
+            self._graph = None
+        self._ensure_bias_table()
+        st = getattr(self, "_dstate", None)
+        if st is None or st[0].device != dev:
+            st = (torch.zeros(1, 1, dtype=torch.long, device=dev), torch.zeros(1, dtype=torch.long, device=dev),
+                  torch.zeros(1, dtype=torch.int32, device=dev))
+            self._dstate = st
+            self._graph = None
+        ids, pos_t, len_t = st
+        ids.fill_(int(token))
+        pos_t.fill_(int(pos))
+        len_t.fill_(int(pos) + 1)
+        from ..pipelines.graphs import CapturedCall, graphs_enabled
+
+        if not graphs_enabled(dev):
+            return self._decode_fn(ids, pos_t, len_t)
+        g = getattr(self, "_graph", None)
+        if g is None:
+            g = CapturedCall(self._decode_fn, ids=ids, pos_t=pos_t, len_t=len_t)
+            self._graph = g
+        return g.run(ids=ids, pos_t=pos_t, len_t=len_t)
 
 
 class T5Tokenizer:

@@ -49,7 +49,10 @@ class MHA(Prepared):
         b, s, _ = ctx.shape
         return ops.gemm(ctx, self.w_in, self.b_in).view(b, s, 2, self.heads, self.dh)
 
-    def forward(self, x, ctx=None, kv=None, residual=None, causal=False):
+    def forward(self, x, ctx=None, kv=None, residual=None, causal=False, cache=None):
+        """``cache`` (self-attention only): a (K, V) pair of [B, cap >= S, H, dh]
+        buffers that receives the keys and values of positions [0, S), taken
+        from the fused projection: the prefill of a KV-cached decode."""
         self._ensure()
         b, s, _ = x.shape
         if self.cross:
@@ -59,6 +62,9 @@ class MHA(Prepared):
         else:
             qkv = ops.gemm(x, self.w_in, self.b_in).view(b, s, 3, self.heads, self.dh)
             q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+            if cache is not None:
+                cache[0][:, :s].copy_(k)
+                cache[1][:, :s].copy_(v)
         o = ops.attention(q, k, v, self.scale, causal=causal)
         return self.o(o.reshape(b, s, self.heads * self.dh), residual=residual)
 
@@ -79,11 +85,26 @@ class PreLNBlock(nn.Module):
         self.fc2 = Linear(mlp_dim, dim, bias=bias)
         self.act = act
 
-    def forward(self, x, ctx=None, causal=False):
-        x = self.attn(self.ln1(x), residual=x, causal=causal)
+    def forward(self, x, ctx=None, causal=False, cache=None):
+        x = self.attn(self.ln1(x), residual=x, causal=causal, cache=cache)
         if self.cross is not None:
             x = self.cross(self.ln_x(x), ctx=ctx, residual=x)
         return self.fc2(self.fc1(self.ln2(x), act=self.act), residual=x)
+
+    def decode(self, x, cache, pos_t, len_t):
+        """One-token step of a block without cross-attention, with device-side
+        position / length (graph-capturable), five launches on the HIP path:
+        the fused QKV GEMV with ln1 in its prologue, the decode attention with
+        the cache append, the out-projection with the residual, fc1 with ln2 and
+        the activation, fc2 with the residual."""
+        a, n1, n2 = self.attn, self.ln1, self.ln2
+        a._ensure()
+        qkv = ops.gemv(x, a.w_in, a.b_in, ln=(n1.weight, n1.bias, n1.eps)).view(1, 1, 3, a.heads, a.dh)
+        o = ops.decode_attention(qkv[:, :, 0], cache[0], cache[1], a.scale, len_t, k_new=qkv[:, :, 1],
+                                 v_new=qkv[:, :, 2], pos=pos_t)
+        x = ops.gemv(o.reshape(1, 1, a.heads * a.dh), a.o.weight, a.o.bias, residual=x)
+        h = ops.gemv(x, self.fc1.weight, self.fc1.bias, act=self.act, ln=(n2.weight, n2.bias, n2.eps))
+        return ops.gemv(h, self.fc2.weight, self.fc2.bias, residual=x)
 
 
 class PostLNBlock(nn.Module):

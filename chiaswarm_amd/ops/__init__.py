@@ -1189,7 +1189,8 @@ def _ref_rope(x, cos, sin):
     return torch.cat((a * cos - b * sin, b * cos + a * sin), -1)
 
 
-def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=None, pos=None, rope=None):
+def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=None, pos=None, rope=None,
+                     rel_bias=None):
     """One query per (b, h) over the first ``kv_len`` keys of a [B, S, Hkv, D] KV
     cache; returns [B, 1, H, D].  ``kv_len``: int32 [1] tensor on q's device,
     clamped to [0, S] (0 gives zeros); on the HIP path the kernel reads it, so
@@ -1204,13 +1205,23 @@ def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=No
     is stored and scored, so the caches hold post-RoPE keys.  ``v_new`` is not
     touched; without ``k_new`` only the query is rotated.
 
+    ``rel_bias``: contiguous fp32 [H, P] table on q's device, P >= S, finite
+    where it is read: key j of head h scores ``q . k_j * scale +
+    rel_bias[h, kv_len - 1 - j]``, a bias indexed by the key's distance to the
+    query's own position kv_len - 1 (T5's causal relative-position bias for the
+    last query row, ALiBi).  The appended key gets ``rel_bias[h, 0]``; entries at
+    distances >= kv_len are never read.  Independent of ``rope`` and of grouped
+    heads.
+
     Definition (CPU / reference): the rotation, that write, the K/V heads
     expanded to the query heads, then ``_ref_attention`` over the first kv_len
-    keys.  HIP: the split-KV decode kernel with all of it fused in for D in
-    {32, 64, 128}; other head dims do the same steps in torch around
-    ``attention(kv_len=)`` (``pos``: optional long [1] device tensor holding
-    kv_len - 1 for that index_copy_, so a caller that has it spares the fallback
-    deriving it)."""
+    keys (with ``rel_bias``: the same softmax with the bias added to the scaled
+    scores).  HIP: the split-KV decode kernel with all of it fused in for D in
+    {32, 64, 80, 128} (80 without ``rope``); other head dims do the same steps in
+    torch around ``attention(kv_len=)``, resp. ``attention(bias=, kv_lens=)`` with
+    the bias row gathered on the device (``pos``: optional long [1] device tensor
+    holding kv_len - 1 for that index_copy_, so a caller that has it spares the
+    fallback deriving it)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or kv_len.device != q.device:
@@ -1230,10 +1241,16 @@ def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=No
                          f"{(B, 1, Hkv, D)}")
     if rope is not None and (D % 2 or len(rope) != 2):
         raise ValueError("decode_attention: rope = (cos, sin) needs an even head dim")
+    if rel_bias is not None and (not isinstance(rel_bias, torch.Tensor) or rel_bias.dtype != torch.float32
+                                 or rel_bias.dim() != 2 or rel_bias.shape[0] != H
+                                 or rel_bias.shape[1] < k_cache.shape[1] or not rel_bias.is_contiguous()
+                                 or rel_bias.device != q.device):
+        raise ValueError(f"decode_attention: rel_bias must be a contiguous fp32 [{H}, P >= {k_cache.shape[1]}] "
+                         "tensor on the device of q")
     if use_hip(q):
         from . import hip_ops
 
-        return hip_ops.decode_attention(q, k_cache, v_cache, scale, kv_len, k_new, v_new, pos, rope)
+        return hip_ops.decode_attention(q, k_cache, v_cache, scale, kv_len, k_new, v_new, pos, rope, rel_bias)
     n = min(max(int(kv_len.reshape(-1)[0].item()), 0), k_cache.shape[1])
     if n == 0:
         return torch.zeros_like(q)
@@ -1248,6 +1265,9 @@ def decode_attention(q, k_cache, v_cache, scale, kv_len, *, k_new=None, v_new=No
     k, v = k_cache[:, :n], v_cache[:, :n]
     if Hkv != H:
         k, v = (t[:, :, :, None].expand(B, n, Hkv, H // Hkv, D).reshape(B, n, H, D) for t in (k, v))
+    if rel_bias is not None:  # key j at distance n - 1 - j from the query
+        bias = rel_bias[:, torch.arange(n - 1, -1, -1, device=q.device)]
+        return _ref_attention_bias(q, k, v, scale, False, bias[:, None])
     return _ref_attention(q, k, v, scale, False)
 
 

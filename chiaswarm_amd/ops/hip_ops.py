@@ -1514,6 +1514,9 @@ sig("csk_attention_decode", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_
     c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p)
 sig("csk_attention_decode_ex", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
     c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p)
+sig("csk_attention_decode_ex2", c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+    c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+    c_int, c_void_p)
 sig("csk_attn_decode_split")
 DECODE = os.environ.get("CSK_DECODE", "1") == "1"
 # kernel launches per op (tests assert the kernels ran)
@@ -1522,7 +1525,7 @@ GEMV_NORM_NONE, GEMV_NORM_LN, GEMV_NORM_RMS = 0, 1, 2  # gemv.hip GV_NORM_*
 GEMV_MAX_M = 8             # gemv.hip GV_MAX_M
 GEMV_LDS_FLOATS = 32768    # gemv.hip GV_LDS_FLOATS: padded rows x K fp32 the kernel keeps in LDS
 DECODE_SPLIT = 64          # attn_decode.hip AD_SPLIT: keys per workgroup
-DECODE_HEAD_DIMS = (32, 64, 128)
+DECODE_HEAD_DIMS = (32, 64, 80, 128)  # 80 (OPT-2.7B) without rope=
 _DECODE_WS: dict = {}      # (device, B, H, S, D) -> (fp32 partials, uint32 counters)
 
 
@@ -1693,10 +1696,14 @@ def _decode_ws(device, B, H, S, D):
     return ws
 
 
-def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None, rope=None):
+def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None, rope=None, rel_bias=None):
     """``ops.decode_attention`` on the HIP path (arguments validated there).
     ``pos``: the caller's long [1] device tensor holding kv_len - 1, used by the
-    fallback's index_copy_ instead of deriving it from ``kv_len``."""
+    fallback's index_copy_ instead of deriving it from ``kv_len``.
+    The kernel takes D in ``DECODE_HEAD_DIMS`` (80 only without ``rope``);
+    ``rel_bias`` (fp32 [H, P >= S]) travels to it as a pointer.  The fallback
+    gathers the [H, 1, S] bias of the query's position on the device and runs
+    ``attention(bias=, kv_lens=)``: no host read either way."""
     for t, n in ((q, "q"), (kc, "k_cache"), (vc, "v_cache"), (k_new, "k_new"), (v_new, "v_new")):
         if t is not None:
             _bf16(t, "decode_attention." + n)
@@ -1717,7 +1724,8 @@ def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None,
         return t is None or (t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:3]))
 
     if (not DECODE or D not in DECODE_HEAD_DIMS or B * H > 65535 or not (vec_ok(kc) and vec_ok(vc))
-            or (cos is not None and (cos.data_ptr() % 16 or sin.data_ptr() % 16))):
+            or (cos is not None and (D == 80 or cos.data_ptr() % 16 or sin.data_ptr() % 16))
+            or (rel_bias is not None and rel_bias.data_ptr() % 16)):
         if (k_new is not None or rope is not None) and pos is None:
             pos = (kv_len.to(torch.long) - 1).clamp_(0, S - 1)
         if rope is not None:
@@ -1732,6 +1740,10 @@ def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None,
             vc.index_copy_(1, pos, v_new)
         if Hkv != H:  # (a copy: this path is for correctness, not speed)
             kc, vc = (t[:, :, :, None].expand(B, S, Hkv, H // Hkv, D).reshape(B, S, H, D) for t in (kc, vc))
+        if rel_bias is not None:  # key j sits at distance kv_len - 1 - j (keys at or past kv_len: masked by kv_lens)
+            dist = (kv_len.to(torch.long) - 1 - torch.arange(S, device=q.device)).clamp_(0, rel_bias.shape[1] - 1)
+            return attention_bias(q, kc, vc, scale, False, rel_bias.index_select(1, dist)[:, None],
+                                  kv_len.clamp(0, S).expand(B).contiguous())
         return attention(q, kc, vc, scale, kv_len=kv_len)
     if not vec_ok(q):
         q = q.contiguous()
@@ -1746,7 +1758,8 @@ def decode_attention(q, kc, vc, scale, kv_len, k_new=None, v_new=None, pos=None,
         return (t.stride(0), t.stride(2)) if t is not None else (0, 0)
 
     st = (c_int64 * 14)(*bh(q), *kc.stride()[:3], *vc.stride()[:3], *bh(k_new), *bh(v_new), *bh(o))
-    _lib.call("csk_attention_decode_ex", _p(o), _p(q), _p(kc), _p(vc), _p(k_new), _p(v_new), st, B, H, Hkv, S, D,
-              float(scale), _p(kv_len), _p(ws), _p(cnt), _p(cos), _p(sin), 0 if cos is None else cos.shape[0], _s())
+    _lib.call("csk_attention_decode_ex2", _p(o), _p(q), _p(kc), _p(vc), _p(k_new), _p(v_new), st, B, H, Hkv, S, D,
+              float(scale), _p(kv_len), _p(ws), _p(cnt), _p(cos), _p(sin), 0 if cos is None else cos.shape[0],
+              _p(rel_bias), 0 if rel_bias is None else rel_bias.shape[1], _s())
     DECODE_STATS["decode_attention"] += 1
     return o

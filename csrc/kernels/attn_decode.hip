@@ -35,6 +35,18 @@
 // key is rotated in fp32 and rounded to bf16 once; that rounded value is both
 // scored and stored, so the cache holds post-RoPE keys and a later step sees
 // exactly what this step used.  v_new is not touched.
+//
+// D = 80 (OPT-2.7B): a row is ten 16-byte chunks.  A key keeps a 16-lane group
+// (as at D = 128: 16 keys per pass, 4 passes) whose lanes 10..15 are idle: they
+// load nothing, hold zeros in q and k, so add 0 to the dot product, and own no
+// output chunk, which leaves the xor reductions over 1..8 and 16..32 as they
+// are.  There is no RoPE at D = 80 (the launcher refuses the tables).
+//
+// Score bias (rb given: fp32 [H][PB], PB >= S): key idx of head h scores
+// q . k * scale + rb[h][n - 1 - idx], a bias indexed by the key's distance to
+// the query's own position n - 1 (T5's causal relative-position bias for the
+// last query row, ALiBi).  It is added in fp32 after the lane reduce and before
+// the running max; only distances [0, n) are read.
 #include "common.h"
 
 #define AD_SPLIT 64     // keys per workgroup
@@ -48,6 +60,7 @@ struct AdArgs {
   const bf16_t* vn;
   const float* cos;  // RoPE tables [P][D / 2] or null
   const float* sin;
+  const float* rb;   // distance-indexed score bias [H][PB] or null
   bf16_t* o;
   float* ws;         // [B * H][nsplit][D + 2] fp32 partials
   unsigned* cnt;     // [B * H] arrival counters, zero between launches
@@ -55,6 +68,7 @@ struct AdArgs {
   int64_t qs[2], ks[3], vs[3], kns[2], vns[2], os[2];  // element strides: (b, h) / (b, s, h)
   int B, H, S, nsplit;
   int rep;           // H / Hkv query heads per K/V head
+  int PB;            // row length of rb
   float scale;
 };
 
@@ -69,9 +83,11 @@ __device__ __forceinline__ void ad_rope8(float* x, const float* xp, const float*
 
 template <int D>
 __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a) {
-  constexpr int LPK = D / 8;              // lanes per key (16-byte chunks of a row)
+  constexpr int NCH = D / 8;              // 16-byte chunks of a row
+  constexpr int LPK = NCH <= 4 ? 4 : NCH <= 8 ? 8 : 16;  // lanes per key: NCH rounded up to a power of two
   constexpr int KPP = AD_THREADS / LPK;   // keys per workgroup pass
-  constexpr int NP = AD_SPLIT / KPP;      // passes: 1 / 2 / 4 at D = 32 / 64 / 128
+  constexpr int NP = AD_SPLIT / KPP;      // passes: 1 / 2 / 4 / 4 at D = 32 / 64 / 80 / 128
+  static_assert(D % 8 == 0 && NCH <= LPK && NCH > LPK / 2, "head dim");
   constexpr int NW = AD_THREADS / 64;
   static_assert(NP >= 1 && NP * KPP == AD_SPLIT, "split / head dim");
   // one LDS object: [NW][D] output partials, [NW] maxima, [NW] sums, the "I am last" word
@@ -91,10 +107,12 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
   const int hk = h / a.rep;                    // the K/V head of this query head
   const bool writer = h - hk * a.rep == 0;     // the one workgroup of the group that stores the appended row
   const int psub = sub ^ (LPK / 2);            // the chunk that holds the rotation partners
+  // D = 80: lanes 10..15 of a key's 16 own no chunk; they load nothing, add 0 to the dot product and hold no output
+  const bool active = NCH == LPK || sub < NCH;
 
   float qf[8], cs[8], sn[8];
-  unpack8(*(const uint4*)(a.q + b * a.qs[0] + h * a.qs[1] + sub * 8), qf);
-  if (a.cos != nullptr) {
+  unpack8(active ? *(const uint4*)(a.q + b * a.qs[0] + h * a.qs[1] + sub * 8) : make_uint4(0u, 0u, 0u, 0u), qf);
+  if (NCH == LPK && a.cos != nullptr) {  // (the launcher takes no RoPE tables where NCH < LPK)
     const int pos = max(n - 1, 0);
     CSK_DCHECK(pos >= 0 && pos < a.S, 3, pos, a.S);
     const int64_t t = (int64_t)pos * (D / 2) + (sub % (LPK / 2)) * 8;
@@ -108,11 +126,17 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
   }
 
   uint4 kr[NP], vr[NP];
+  float rb[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     const int idx = split * AD_SPLIT + p * KPP + slot;
     kr[p] = vr[p] = make_uint4(0u, 0u, 0u, 0u);
-    if (idx < n) {
+    rb[p] = 0.f;
+    if (a.rb != nullptr && idx < n) {  // the bias of distance n - 1 - idx, in [0, n) and so inside the row
+      CSK_DCHECK(n - 1 - idx >= 0 && n - 1 - idx < a.PB, 4, n - 1 - idx, a.PB);
+      rb[p] = a.rb[(int64_t)h * a.PB + (n - 1 - idx)];
+    }
+    if (idx < n && active) {
       CSK_DCHECK(idx >= 0 && idx < a.S, 1, idx, a.S);
       bf16_t* kp = a.kc + b * a.ks[0] + (int64_t)idx * a.ks[1] + hk * a.ks[2] + sub * 8;
       bf16_t* vp = a.vc + b * a.vs[0] + (int64_t)idx * a.vs[1] + hk * a.vs[2] + sub * 8;
@@ -120,7 +144,7 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
         const bf16_t* kn = a.kn + b * a.kns[0] + hk * a.kns[1];
         kr[p] = *(const uint4*)(kn + sub * 8);
         vr[p] = *(const uint4*)(a.vn + b * a.vns[0] + hk * a.vns[1] + sub * 8);
-        if (a.cos != nullptr) {
+        if (NCH == LPK && a.cos != nullptr) {
           float kf[8], kq[8];
           unpack8(kr[p], kf);
           unpack8(*(const uint4*)(kn + psub * 8), kq);
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
     for (int j = 0; j < 8; ++j) d = __builtin_fmaf(qf[j], kf[j], d);
 #pragma unroll
     for (int o = 1; o < LPK; o <<= 1) d += __shfl_xor(d, o, 64);  // the key's LPK lanes are one aligned group of a wave
-    s[p] = idx < n ? d * a.scale : ninf;
+    s[p] = idx < n ? d * a.scale + rb[p] : ninf;  // (no table: + 0, the same value)
     m = fmaxf(m, s[p]);
   }
   m = wave_max(m);
@@ -177,7 +201,7 @@ __global__ __launch_bounds__(AD_THREADS) void attn_decode_kernel(const AdArgs a)
 #pragma unroll
     for (int j = 0; j < 8; ++j) of[j] += __shfl_xor(of[j], o, 64);
   l = wave_sum(l);
-  if (lane < LPK) {
+  if (lane < NCH) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) sm_o[wave * D + lane * 8 + j] = of[j];
   }
@@ -257,18 +281,22 @@ static bool ad_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // ws: fp32 [B * H * ceil(S / AD_SPLIT) * (D + 2)]; cnt: uint32 [B * H], zero on entry, zero on exit.
 // Graph-capturable: no allocation, no sync.
 // Hkv: K/V heads of the caches and of k_new / v_new (H % Hkv == 0; their head strides in st are per K/V head).
-// cos / sin: fp32 [P][D / 2] RoPE tables, P >= S, 16-byte aligned, or both null.
-CSK_API int csk_attention_decode_ex(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
-                                    const int64_t* st, int B, int H, int Hkv, int S, int D, float scale,
-                                    const void* kv_len, void* ws, void* cnt, const void* cos, const void* sin, int P,
-                                    hipStream_t stream) {
+// cos / sin: fp32 [P][D / 2] RoPE tables, P >= S, 16-byte aligned, or both null (D = 80 takes none).
+// rel_bias: fp32 [H][PB] with PB >= S, 16-byte aligned, or null: key idx of head h scores
+// q . k * scale + rel_bias[h][n - 1 - idx], n = clamp(*kv_len, 0, S).
+CSK_API int csk_attention_decode_ex2(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
+                                     const int64_t* st, int B, int H, int Hkv, int S, int D, float scale,
+                                     const void* kv_len, void* ws, void* cnt, const void* cos, const void* sin, int P,
+                                     const void* rel_bias, int PB, hipStream_t stream) {
   if (Hkv < 1 || H % Hkv != 0 || (cos == nullptr) != (sin == nullptr) || (cos != nullptr && P < S) ||
       !ad_aligned16(cos) || !ad_aligned16(sin))
+    return (int)hipErrorInvalidValue;
+  if ((cos != nullptr && D == 80) || (rel_bias != nullptr && PB < S) || !ad_aligned16(rel_bias))
     return (int)hipErrorInvalidValue;
   if (o == nullptr || q == nullptr || kc == nullptr || vc == nullptr || st == nullptr || kv_len == nullptr ||
       ws == nullptr || cnt == nullptr || (kn == nullptr) != (vn == nullptr))
     return (int)hipErrorInvalidValue;
-  if ((D != 32 && D != 64 && D != 128) || B < 1 || H < 1 || S < 1 || (int64_t)B * H > 65535)
+  if ((D != 32 && D != 64 && D != 80 && D != 128) || B < 1 || H < 1 || S < 1 || (int64_t)B * H > 65535)
     return (int)hipErrorInvalidValue;
   if (!ad_aligned16(q) || !ad_aligned16(kc) || !ad_aligned16(vc) || !ad_aligned16(kn) || !ad_aligned16(vn))
     return (int)hipErrorInvalidValue;
@@ -283,12 +311,22 @@ CSK_API int csk_attention_decode_ex(void* o, const void* q, void* kc, void* vc, 
   a.kns[0] = st[8]; a.kns[1] = st[9]; a.vns[0] = st[10]; a.vns[1] = st[11];
   a.os[0] = st[12]; a.os[1] = st[13];
   a.cos = (const float*)cos; a.sin = (const float*)sin; a.rep = H / Hkv;
+  a.rb = (const float*)rel_bias; a.PB = PB;
   a.B = B; a.H = H; a.S = S; a.nsplit = (S + AD_SPLIT - 1) / AD_SPLIT; a.scale = scale;
   const dim3 grid(a.nsplit, B * H);
   if (D == 32) hipLaunchKernelGGL(attn_decode_kernel<32>, grid, dim3(AD_THREADS), 0, stream, a);
   else if (D == 64) hipLaunchKernelGGL(attn_decode_kernel<64>, grid, dim3(AD_THREADS), 0, stream, a);
+  else if (D == 80) hipLaunchKernelGGL(attn_decode_kernel<80>, grid, dim3(AD_THREADS), 0, stream, a);
   else hipLaunchKernelGGL(attn_decode_kernel<128>, grid, dim3(AD_THREADS), 0, stream, a);
   CSK_CHECK_LAUNCH();
+}
+
+CSK_API int csk_attention_decode_ex(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
+                                    const int64_t* st, int B, int H, int Hkv, int S, int D, float scale,
+                                    const void* kv_len, void* ws, void* cnt, const void* cos, const void* sin, int P,
+                                    hipStream_t stream) {
+  return csk_attention_decode_ex2(o, q, kc, vc, kn, vn, st, B, H, Hkv, S, D, scale, kv_len, ws, cnt, cos, sin, P,
+                                  nullptr, 0, stream);
 }
 
 CSK_API int csk_attention_decode(void* o, const void* q, void* kc, void* vc, const void* kn, const void* vn,
